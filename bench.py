@@ -14,21 +14,25 @@ shard with no data-path collective; the only collective is one all-reduce (RCCL)
 of the 4-double metric vector at the end of the rollout.
 
 Order of a run: build check (before anything touches the GPU) -> reset -> P untimed
-pre-warm steps (``--prewarm-steps``, reported, and each of them timed with its own pair of
-HIP events: ``roofline.prewarm_series`` shows the cold start -- a fresh process runs
-launches ~10-100 slower than the settled kernel and the driver's default ``--steps 20
---warmup 5`` is 3 ms of work) -> R more untimed steps (``--rewarm-steps``, reported: reading the
-pre-warm pass's 1 500 timers leaves the chip idle for a few ms, and an idle of 3 / 10 ms costs the
-next 20 launches 5 / 15-20 %, tools/idle_probe.py) flowing without a host-side gap into the
+pre-warm steps (``--prewarm-steps``, reported; a fresh process runs launches ~10-100 slower
+than the settled kernel and the driver's default ``--steps 20 --warmup 5`` is 3 ms of work)
+-> R more untimed steps (``--rewarm-steps``, reported) flowing without a host-side gap into the
 W untimed warm-up steps -> barrier + synchronize ->
 EXACTLY K timed steps (``value`` / ``ms_per_step`` / ``roofline.kernel_ms`` come from here;
 nothing but the K launches and two HIP events is in the region) -> barrier + synchronize ->
-the same K steps once more with a pair of HIP events around EVERY launch
-(``roofline.series``) -> the same workload through ``sgw_rollout`` (``fused_rollout``) ->
-end-of-rollout metric all-reduce -> (rank 0, N=1) the other 1-GPU BASELINE shapes, briefly
-(``configs``: config 2, config 5's per-GPU share, config 3 at 524 288 envs) -> the CPU
-baseline -> the envs the CPU baseline played, replayed on the GPU and compared
-(``rollout.checked_vs_oracle``).
+(``--dump-outputs DIR``) what the last timed step left, as DIR/<name>.npy -> end-of-rollout
+metric all-reduce -> the JSON line.
+
+``--full`` adds everything that is not the headline figure, in this order: each pre-warm step
+timed with its own pair of HIP events (``roofline.prewarm_series`` shows the cold start; reading
+its 1 500 timers leaves the chip idle for a few ms, and an idle of 3 / 10 ms costs the next 20
+launches 5 / 15-20 %, tools/idle_probe.py -- what the re-warm steps are for) -> after the timed
+region, the same K steps once more with a pair of HIP events around EVERY launch
+(``roofline.series``) -> the same workload through ``sgw_rollout`` (``fused_rollout``) -> (rank 0,
+N=1) the timed engine checked against the C oracle, the policy-driven turn, a write-only probe,
+the other 1-GPU BASELINE shapes, briefly (``configs``: config 2, config 5's per-GPU share, config 3
+at 524 288 envs), the Python API legs -> the CPU baseline -> the envs the CPU baseline played,
+replayed on the GPU and compared (``rollout.checked_vs_oracle``).
 
 Prints ONE JSON line on rank 0.
 """
@@ -523,11 +527,14 @@ def many_agents_turn_bench(dev, envs: int = 2048, turns: int = 60):
 
 def ensure_built() -> None:
     """Both native libraries, checked (and, outside a profiler, rebuilt if stale) BEFORE torch or anything else touches
-    the GPU: no compiler is ever started from a GPU-initialised process.  Ranks of one node take turns on a lock."""
+    the GPU: no compiler is ever started from a GPU-initialised process.  Ranks of one node take turns on a lock, taken only
+    when something has to be built: a benchmark of a built tree writes nothing into it (its user may not be allowed to)."""
     import fcntl
 
     import __graft_entry__ as graft
 
+    if graft.libs_up_to_date():
+        return
     profiled = any(k.startswith(("ROCPROF", "ROCPROFILER")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
     with open(os.path.join(ROOT, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -582,6 +589,40 @@ def series_stats(ms):
             "mean_ms": sum(ms) / len(ms), "first5_mean_ms": sum(ms[:5]) / len(ms[:5])}
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def gather_outputs(eng):
+    """What a caller of ``sgw_step`` holds after the last timed step, copied to the host: the step's observations, actions and
+    rewards and the state it leaves (grid, positions, float64 totals), as float32 (totals float64).  When the whole batch would
+    exceed DUMP_BUDGET_BYTES, a fixed sample of envs (seed 0, ascending ids) stands for it; ``env_ids`` names them."""
+    import numpy as np
+    import torch
+
+    tensors = {"obs": eng.obs, "actions": eng.actions, "rewards": eng.rewards, "grid": eng.grid, "agent_pos": eng.agent_pos,
+               "total_reward": eng.total_reward}
+    E = eng.num_envs
+    per_env = 8 + sum(t[0].numel() * (8 if t.dtype == torch.float64 else 4) for t in tensors.values())
+    n = min(E, DUMP_BUDGET_BYTES // per_env)
+    local = np.arange(E) if n == E else np.sort(np.random.default_rng(0).choice(E, size=n, replace=False))
+    idx = torch.from_numpy(local).to(eng.device)
+    out = {"env_ids": (local + eng.first_env_id).astype(np.float64)}
+    for name, t in tensors.items():
+        picked = t.index_select(0, idx)
+        out[name] = picked.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    return out
+
+
+def write_outputs(directory: str, arrays) -> dict:
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": directory, "files": sorted(name + ".npy" for name in arrays), "envs": int(arrays["env_ids"].shape[0]),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -598,10 +639,10 @@ def main() -> int:
                     help="epoch length: every env is auto-reset (K3, inside sgw_step) after this many turns, inside the "
                          "timed loop too; 0 = one endless epoch (SURVEY 8d: no reset in the timed region)")
     ap.add_argument("--turns-per-launch", type=int, default=50,
-                    help="after the timed region: the same workload through sgw_rollout, this many turns per call (the env's "
+                    help="--full: after the timed region, the same workload through sgw_rollout, this many turns per call (the env's "
                          "grid stays in LDS from turn to turn); reported beside the per-turn numbers as fused_rollout; 0 = skip")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-series", action="store_true", help="skip the per-launch timing pass after the timed region")
+    ap.add_argument("--no-series", action="store_true", help="--full without the per-launch timing pass after the timed region")
     ap.add_argument("--graph", action="store_true",
                     help="replay ONE hipGraph of the K timed launches instead of calling sgw_step K times (same launches, same turn numbers, same "
                          "results; measured on the headline: 0.7 us more per launch between the events, 0.8 us less on the wall clock)")
@@ -612,12 +653,21 @@ def main() -> int:
                     help="u8 = compact one-hot counts (an extra, reported separately; the contract format is f32)")
     ap.add_argument("--no-sweep", action="store_true", help="diagnostic: skip the entity sweep (NOT a valid bench line)")
     ap.add_argument("--no-side-configs", action="store_true",
-                    help="skip the short runs of the other 1-GPU BASELINE shapes (config 2, config 5's per-GPU share, config 3 at "
+                    help="--full without the short runs of the other 1-GPU BASELINE shapes (config 2, config 5's per-GPU share, config 3 at "
                          "524 288 envs) that the headline run adds to the line as `configs`")
-    ap.add_argument("--side-steps", type=int, default=100, help="timed launches of each side config")
+    ap.add_argument("--side-steps", type=int, default=100, help="timed launches of each side config (--full)")
     ap.add_argument("--no-self-check", action="store_true",
-                    help="skip replaying the CPU baseline's envs on the GPU and comparing the results (rollout.checked_vs_oracle)")
+                    help="--full without replaying the CPU baseline's envs on the GPU and comparing the results (rollout.checked_vs_oracle)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (per-launch series, sgw_rollout, the oracle "
+                         "self-checks, the policy turn, the side configs, the Python API legs, the CPU baseline); the --no-* "
+                         "options above leave out parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's envs) to DIR/<name>.npy as float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of envs when the batch's outputs are larger")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     ensure_built()
 
@@ -715,10 +765,13 @@ def main() -> int:
             eng.turn = saved_turn
         torch.cuda.synchronize(dev)
 
-    # the pre-warm pass: untimed for `value`, but every launch of it sits between its own pair of HIP events, so the line
+    # the pre-warm pass: untimed for `value`; with --full every launch of it sits between its own pair of HIP events, so the line
     # shows the cold start next to the settled kernel
     prewarm_series = None
-    if args.prewarm_steps > 0:
+    if args.prewarm_steps > 0 and not args.full:
+        for _ in range(args.prewarm_steps):
+            step()
+    elif args.prewarm_steps > 0:
         eng.set_timing(True)
         for _ in range(args.prewarm_steps):
             step()
@@ -756,11 +809,13 @@ def main() -> int:
     barrier()
     dt = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events over the timed region, per launch
+    # what the last timed step left, copied before anything else launches (written to disk at the end)
+    dumped = gather_outputs(eng) if args.dump_outputs and rank == 0 else None
 
     # the same K steps again, every launch between its own pair of HIP events (outside the timed region: two event
     # packets per launch would sit in the measured stream otherwise)
     series = None
-    if not args.no_series:
+    if args.full and not args.no_series:
         eng.set_timing(True)
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -780,7 +835,7 @@ def main() -> int:
     # per-turn launch does not describe it; its own HBM-side bytes are the observation / action / reward / position
     # writes of every turn plus one grid read + write-back per call)
     fused = None
-    if args.turns_per_launch > 0 and write_obs and sweep and args.diag_agents < 0 and args.max_turns == 0:
+    if args.full and args.turns_per_launch > 0 and write_obs and sweep and args.diag_agents < 0 and args.max_turns == 0:
         T = max(1, min(args.turns_per_launch, args.steps))
         calls = max(1, args.steps // T)
         eng.rollout(T)                                  # warm
@@ -913,13 +968,13 @@ def main() -> int:
         if fused is not None:
             rf["c3_rollout_ms_per_turn"] = fused["ms_per_step"]
             rf["c3_rollout_algorithmic_frac"] = alg_bytes / (fused["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-        if world == 1 and valid_line and not args.no_self_check and args.max_turns == 0:
+        if args.full and world == 1 and valid_line and not args.no_self_check and args.max_turns == 0:
             # the self-check of the headline on the engine (and code object) that was just timed: from the state its launches ended in
             chk = continue_against_oracle(eng, spec, 3)
             out["rollout"]["timed_engine_checked_vs_oracle"] = chk
             rf["timed_engine_checked_equal"] = chk["equal"]
             rf["timed_engine_checked_what"] = f"{chk['envs']} envs x {chk['turns']} turns from turn {chk['from_turn']} on {chk['kernel']} vs the C oracle, all tensors"
-        if world == 1 and valid_line and not args.no_side_configs and args.max_turns == 0:
+        if args.full and world == 1 and valid_line and not args.no_side_configs and args.max_turns == 0:
             out["policy_turn"] = policy_turn_bench(eng)          # (after every timed region of the headline; same engine)
             pt = out["policy_turn"]
             for key in ("fused_turn_ms", "policy_turn_ms", "policy_turn_replay_rows_ms", "policy_turn_replay_rows_one_launch_ms"):
@@ -927,7 +982,7 @@ def main() -> int:
                     rf[key] = pt[key]
             out["roofline"]["write_only_probe"] = write_only_probe(dev, eng.obs.numel() * eng.obs.element_size())
             rf["write_only_tb_per_s"] = rf["write_only_probe"]["tb_per_s"]
-        if world == 1 and args.config == "c3" and valid_line and not args.no_side_configs:
+        if args.full and world == 1 and args.config == "c3" and valid_line and not args.no_side_configs:
             # the other 1-GPU BASELINE shapes, briefly, AFTER the headline run (its numbers are not touched by them)
             eng_obs, eng.obs = eng.obs, None                       # give the headline's 617 MB observation tensor back first
             del eng_obs
@@ -975,10 +1030,12 @@ def main() -> int:
             for key in ("eager_loop", "speculative", "speculative_equals_eager"):
                 if key in ma:
                     rf[f"take_turn_c5_{key}" + ("" if key.endswith("eager") else "_us")] = ma[key]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], played = cpu_baseline(spec, args.config, args.cpu_seconds)
             if valid_line and not args.no_self_check:
                 out["rollout"]["checked_vs_oracle"] = check_against_oracle(spec, played, dev, obs_dtype)
+        if dumped is not None:
+            out["outputs"] = write_outputs(args.dump_outputs, dumped)
         print(json.dumps(out), flush=True)
     if grouped:
         barrier()

@@ -1139,6 +1139,92 @@ def make_buffer_fixture():
     sg.save(path)
     print(f"  wrote {path} ({os.path.getsize(path)} bytes)")
 
+
+# --------------------------------------------------------------------------- #
+# tests/test_oracle_vs_reference.py: random cases, and what the reference produced for them
+# --------------------------------------------------------------------------- #
+VS_REFERENCE_DIR = os.path.join(GOLDEN_DIR, "vs_reference")
+VS_REFERENCE_CASES = {"treasurehunt": 10, "tag": 4, "cleanup": 3}
+
+
+def random_case(kind, case):
+    """Case `case` of `kind`: shape, agent count, radius, rates, seed, env ids, turns drawn from a generator seeded by the case.
+    Returns (spec, env ids, turns, keyword arguments of the reference run, keyword arguments of check_against_oracle)."""
+    if kind == "treasurehunt":
+        rng = np.random.default_rng(31000 + case)
+        h, w = int(rng.integers(6, 20)), int(rng.integers(6, 20))
+        r = int(rng.integers(1, min((min(h, w) - 1) // 2, 4) + 1))
+        a = int(rng.integers(1, min(7, (h - 2) * (w - 2) // 3) + 1))
+        spec = O.treasurehunt_spec(h, w, a, r, spawn_prob=float(rng.choice([0.0, 0.01, 0.08, 0.5])), seed=int(rng.integers(0, 2**40)),
+                                   dense_prob=float(rng.choice([0.0, 0.0, 0.2, 0.6])))
+        ids = [int(v) for v in rng.integers(0, 2**31, size=2)]
+        turns, epoch = int(rng.integers(3, 9)), int(rng.integers(0, 12))
+        return spec, ids, turns, {"epoch": epoch}, {"epoch": epoch}
+    if kind == "tag":
+        rng = np.random.default_rng(32000 + case)
+        h, w = int(rng.integers(6, 13)), int(rng.integers(6, 13))
+        r = int(rng.integers(1, min((min(h, w) - 1) // 2, 3) + 1))
+        a = int(rng.integers(2, 7))
+        spec = tag_spec(h, w, a, r, seed=int(rng.integers(0, 2**40)), reward_per_turn=int(rng.choice([10, 1, 3])))
+        ids = [int(v) for v in rng.integers(0, 2**31, size=2)]
+        turns = int(rng.integers(4, 12))
+        return spec, ids, turns, {}, {}
+    if kind == "cleanup":
+        rng = np.random.default_rng(33000 + case)
+        h, w = int(rng.integers(12, 19)), int(rng.integers(12, 19))
+        r = int(rng.integers(1, 4))
+        a = int(rng.integers(1, 5))
+        spec = cleanup_spec(h, w, a, r, seed=int(rng.integers(0, 2**40)), beam_radius=int(rng.integers(1, 4)),
+                            pollution_p=float(rng.choice([0.02, 0.1])), apple_p=float(rng.choice([0.01, 0.06])))
+        ids = [int(v) for v in rng.integers(0, 2**31, size=2)]
+        turns = int(rng.integers(6, 15))
+        return spec, ids, turns, {"initial_apples": int(rng.integers(1, 6))}, {"injected": True}
+    raise ValueError(kind)
+
+
+def make_vs_reference_fixtures(R):
+    runners = {"treasurehunt": run_reference_treasurehunt, "tag": run_reference_tag, "cleanup": run_reference_cleanup}
+    os.makedirs(VS_REFERENCE_DIR, exist_ok=True)
+    for kind, n in VS_REFERENCE_CASES.items():
+        for case in range(n):
+            spec, ids, turns, run_kw, check_kw = random_case(kind, case)
+            out = runners[kind](R, spec, ids, turns, **run_kw)
+            check_against_oracle(spec, ids, turns, out, **check_kw)
+            save(os.path.join("vs_reference", f"{kind}_{case}"), spec, ids, out)
+    make_buffer_files_read_by_reference()
+
+
+def make_buffer_files_read_by_reference():
+    """tests/test_buffer_files.py::test_reference_loader_reads_product_files: the files the product's Buffer / SavedGames write for
+    that test's histories, and what the reference's own Buffer.load (sorrel/buffers.py:181-201) read from them."""
+    import tempfile
+
+    from tests.test_buffer_files import _batched, _replay_ring
+
+    ref_loader.install()
+    from sorrel.buffers import Buffer as RefBuffer
+
+    payload = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        one, _ = _replay_ring()
+        one.save(os.path.join(tmp, "one.npz"))
+        sg = _batched()
+        sg.save(os.path.join(tmp, "b.npz"))
+        for tag, name in (("one", "one.npz"), ("batched", "b.npz")):
+            with np.load(os.path.join(tmp, name)) as d:
+                payload.update({f"file_{tag}__{k}": d[k] for k in d.files})
+        r = RefBuffer.load(os.path.join(tmp, "one.npz"))
+        rb = RefBuffer.load(os.path.join(tmp, "b.npz"))
+    s, _a, _rwd, ns, _d, _valid = rb.sample(2)
+    payload.update(ref_one__capacity=np.int64(r.capacity), ref_one__idx=np.int64(r.idx), ref_one__n_frames=np.int64(r.n_frames),
+                   ref_one__states=r.states, ref_one__actions=r.actions, ref_one__current_state=r.current_state(),
+                   ref_batched__capacity=np.int64(rb.capacity), ref_batched__states=rb.states, ref_batched__actions=rb.actions,
+                   ref_batched__sample_s_shape=np.asarray(s.shape), ref_batched__sample_ns_shape=np.asarray(ns.shape))
+    path = os.path.join(VS_REFERENCE_DIR, "buffer_files_read_by_reference.npz")
+    np.savez_compressed(path, **payload)
+    print(f"  wrote {path} ({os.path.getsize(path)} bytes)")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["buffers"]:      # only the replay-buffer fixtures
         make_buffer_fixture()
@@ -1151,6 +1237,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["round6"]:       # only the fixtures added in round 6
         make_round6_fixtures(_import_reference())
+        sys.exit(0)
+    if sys.argv[1:] == ["vs_reference"]:     # only the stored cases of tests/test_oracle_vs_reference.py and the buffer-file read-back
+        make_vs_reference_fixtures(_import_reference())
         sys.exit(0)
     if sys.argv[1:] == ["round3"]:       # only the fixtures added in round 3
         make_round3_fixtures(_import_reference())

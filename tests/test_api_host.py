@@ -617,14 +617,19 @@ def test_alias_imports_leave_the_mirrors_module_specs_alone():
 
     from sorrel_amd import compat
 
+    import sorrel_amd.buffers as own
+
+    # the reload rebinds Buffer & co. to new class objects; later tests in this process hold the old ones (isinstance checks would fail)
+    saved = dict(own.__dict__)
     compat.install()
     try:
         import sorrel.buffers as aliased
-        import sorrel_amd.buffers as own
 
         assert aliased is own and own.__spec__.name == "sorrel_amd.buffers" and own.__name__ == "sorrel_amd.buffers"
         assert importlib.reload(own) is own
     finally:
+        own.__dict__.clear()
+        own.__dict__.update(saved)
         compat.uninstall() if hasattr(compat, "uninstall") else None
 
 

@@ -47,11 +47,11 @@ def test_bench_two_ranks_run_the_product_and_agree_with_one_process(built):
 
 
 def test_bench_line_carries_side_configs_cold_start_and_the_oracle_self_check(built):
-    """The driver's line (N = 1, config 3) with short settings: `configs` holds config 2, config 5's per-GPU share and
+    """The full line (``--full``; N = 1, config 3) with short settings: `configs` holds config 2, config 5's per-GPU share and
     config 3 at 524 288 envs, each with kernel_ms / roofline / kernel; `prewarm_series` shows the cold start; the envs the
     CPU baseline played are replayed on the GPU and must be equal (rollout.checked_vs_oracle)."""
     line = _run_bench(["--gpus", "1", "--steps", "10", "--warmup", "2", "--prewarm-steps", "120", "--side-steps", "10",
-                       "--cpu-seconds", "2", "--turns-per-launch", "5"], 1, {})
+                       "--cpu-seconds", "2", "--turns-per-launch", "5", "--full"], 1, {})
     assert set(line["configs"]) == {"c2", "c5", "c3_524288"}
     for name, c in line["configs"].items():
         assert c["kernel_ms"] > 0 and 0.0 < c["roofline"]["frac"] < 1.5 and c["status"] == 0, name
@@ -109,3 +109,37 @@ def test_bench_timed_region_as_a_graph_plays_the_same_rollout(built):
         assert "hipGraph" in a["timed_region_submission"] and b["timed_region_submission"] == "K sgw_step calls"
         assert a["rollout"]["sum_total_reward"] == b["rollout"]["sum_total_reward"] and a["rollout"]["status"] == b["rollout"]["status"] == 0
         assert a["steps"] == b["steps"] == 9 and a["roofline"]["kernel_ms"] > 0
+
+
+# ------------------------------------------------------------------ bench.py --dump-outputs: what the timed path computed
+def test_bench_dump_outputs_are_what_the_last_timed_step_left(built, tmp_path):
+    """A plain line (no --full) with --dump-outputs: it reports the headline alone, and the files hold what the K-th timed sgw_step
+    left -- observations, actions, rewards, grid, positions, float64 totals of a seeded sample of envs (the batch's outputs exceed
+    the 64 MB budget) -- equal to the C oracle played from reset through exactly W + K turns.  A second run that submits the timed
+    launches as one hipGraph writes the same files.  This test makes no GPU call itself."""
+    from sorrel_amd.spec import treasurehunt_spec
+
+    E, W, K = 8192, 2, 5
+    common = ["--gpus", "1", "--envs", str(E), "--steps", str(K), "--warmup", str(W), "--prewarm-steps", "0"]
+    a = _run_bench(common + ["--dump-outputs", str(tmp_path / "a")], 1, {})
+    b = _run_bench(common + ["--graph", "--dump-outputs", str(tmp_path / "b")], 1, {})
+    assert a["steps"] == K and a["ms_per_step"] > 0 and a["value"] > 0 and a["rollout"]["status"] == 0
+    assert "configs" not in a and "cpu_baseline" not in a and "policy_turn" not in a
+    assert a["roofline"]["series"] is None and a["roofline"]["prewarm_series"] is None and a["fused_rollout"] is None
+    names = ("env_ids", "obs", "actions", "rewards", "grid", "agent_pos", "total_reward")
+    assert sorted(a["outputs"]["files"]) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names) <= 64e6
+    da = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    db = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    for n in names:
+        assert da[n].dtype == (np.float64 if n in ("env_ids", "total_reward") else np.float32), n
+        assert np.array_equal(da[n], db[n]), n
+    ids = da["env_ids"].astype(np.int64)
+    assert 0 < len(ids) == a["outputs"]["envs"] < E and np.all(np.diff(ids) > 0) and ids[-1] < E
+    co = H.COracle(treasurehunt_spec(32, 32, 8, 3, spawn_prob=0.005, seed=0, dense_prob=0.0), E)
+    co.reset(0)
+    for t in range(1, W + K + 1):
+        co.step(0, t, random_actions=True)
+    for n, ref in (("obs", co.obs), ("actions", co.actions), ("rewards", co.rewards), ("grid", co.grid), ("agent_pos", co.pos),
+                   ("total_reward", co.total)):
+        assert np.array_equal(da[n], ref[ids].astype(da[n].dtype)), n

@@ -9,7 +9,7 @@ python3 -c 'import sys; sys.path.insert(0, "'$REPO'"); import __graft_entry__ as
 if [ "$PART" = "1" ]; then
   bash $REPO/tools/profile_gpu.sh r03_c3 > $OUT/profile_r03_c3.log 2>&1 || exit 1
   echo headline profile done
-  cd $REPO && timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err || exit 1
+  cd $REPO && timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err || exit 1
   echo driver-flags line done
   timeout -k 10 300 python3 tools/ramp.py > $OUT/launch_ramp.txt 2>&1 || exit 1
   echo ramp done

@@ -13,7 +13,7 @@ if [ "$PART" = "1" ]; then
   bash $REPO/tools/profile_gpu.sh r06_c3 > $OUT/profile_r06_c3.log 2>&1 || exit 1
   find $OUT/prof_r06_c3 -name "*kernel_trace.csv" -delete; find $OUT/prof_r06_c3 -name "*counter_collection.csv" -delete
   echo headline profile done
-  cd $REPO && timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/r06_bench_driver_flags.json 2> $OUT/r06_bench_driver_flags.err || exit 1
+  cd $REPO && timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/r06_bench_driver_flags.json 2> $OUT/r06_bench_driver_flags.err || exit 1
   echo driver-flags line done
 elif [ "$PART" = "2" ]; then
   cd /tmp && export TMPDIR=/tmp
