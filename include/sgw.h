@@ -105,6 +105,8 @@ extern "C" {
 #define SGW_STREAM_DENSE_KIND 5
 #define SGW_STREAM_TAG_INIT 6
 #define SGW_STREAM_EXPLORE 7           /* index = agent: the epsilon test of SGW_ACT_QF32 (sgw_turn_epsilon) */
+#define SGW_STREAM_VALUE 8             /* index = layer-major cell index of the TARGET cell (the spawn stream's index), turn = the turn in
+                                        * flight: which of its two values a type with value_alt_prob > 0 is worth this turn */
 
 /* what Agent.act does (sgw_config.agent_rule) */
 #define SGW_AGENT_RULE_MOVE 0 /* MovingAgent.act: reward = value of the target, then move (sorrel/agents/agent.py:215-225) */
@@ -198,6 +200,13 @@ typedef struct sgw_config {
     int32_t reward_total_factor; /* how many times act's reward enters total_reward (0 = 1; Cleanup = 2) */
     int64_t grid_env_stride; /* bytes between consecutive envs in `grid`; 0 = dense (L*H*W).  A stride that is a
                               * multiple of 16 lets worlds of any byte count use the 16-byte load/store kernels */
+    /* Drawn values (0.3; a pure suffix: every field above keeps its offset).  An entity whose value is redrawn every turn between two
+     * outcomes (Deck.transition, sorrel/examples/iowa/entities.py:45-70): a type with value_alt_prob[t] > 0 is worth type_value_alt[t]
+     * when u32(SGW_STREAM_VALUE, index = cell) < floor(value_alt_prob[t] * 2^32) (SGW_RULE_SPAWN's threshold convention), else
+     * type_value[t].  The draw is a function of (seed, env, epoch, turn, cell): it is made when an agent targets the cell and never
+     * stored.  SGW_AGENT_RULE_MOVE only, not on agent types; all zero = no type draws. */
+    double type_value_alt[SGW_MAX_TYPES];
+    double value_alt_prob[SGW_MAX_TYPES];
 } sgw_config;
 
 typedef struct sgw_engine sgw_engine;
@@ -320,6 +329,12 @@ int sgw_init_agent_state(sgw_engine* eng, uint8_t* agent_state, void* stream);
 /* Facing of every agent, uint8 [E][A]: 0 up, 1 right, 2 down, 3 left (MovingAgent.direction; CleanupAgent
  * starts at 2).  Caller-initialised; sgw_step updates it on move actions and reads it to aim beams. */
 int sgw_bind_agent_dir(sgw_engine* eng, uint8_t* agent_dir);
+/* What every agent stepped on, uint8 [E][A] (GamblingAgent.encounters counts it per kind, sorrel/examples/iowa/agents.py:54-56): once
+ * bound, every act of SGW_AGENT_RULE_MOVE -- sgw_step, sgw_rollout, sgw_act / sgw_turn_act*, the commit of sgw_turn_resolve -- writes the
+ * type id world.observe(new_location) returned for that agent this turn, 255 for an agent whose action was invalid or whose target lies
+ * outside the grid.  Written by the lane that writes the reward; NULL unbinds (nothing is written, nothing is paid).  sgw_rollout has no
+ * turn stride for it: the tensor holds the LAST turn of the call. */
+int sgw_bind_target_types(sgw_engine* eng, uint8_t* target_types);
 
 /* Observation element type written by sgw_step / sgw_observe.  SGW_OBS_F32 (default) is the contract
  * format (the reference's replay buffer stores float32, sorrel/buffers.py:31).  SGW_OBS_U8 is a

@@ -19,7 +19,7 @@ or, without touching the script at all::
 ``install`` registers a meta-path finder that answers every ``sorrel`` / ``sorrel.*`` import with the ``sorrel_amd``
 module of the same relative name (the SAME module object: ``sorrel.environment.Environment is
 sorrel_amd.environment.Environment``).  Parts of the reference outside the hot path this package rebuilds (models beyond
-``BaseModel`` / ``RandomModel``, logging, visualisation, the CLI, NodeWorld, chess / iowa) do not exist here; importing
+``BaseModel`` / ``RandomModel``, logging, visualisation, the CLI, NodeWorld, chess) do not exist here; importing
 them fails with a ``ModuleNotFoundError`` that says so.  If a real ``sorrel`` distribution is importable, ``install``
 refuses to shadow it unless ``force=True``.
 """
@@ -38,7 +38,7 @@ MIRRORED = (
     "", "environment", "worlds", "worlds.gridworld", "entities", "entities.entity", "entities.basic_entities", "agents",
     "agents.agent", "observation", "observation.observation_spec", "observation.visual_field", "observation.embedding",
     "action", "action.action_spec", "utils", "utils.helpers", "location", "buffers", "models", "models.base_model",
-    "examples", "examples.treasurehunt", "examples.tag", "examples.cleanup",
+    "examples", "examples.treasurehunt", "examples.tag", "examples.cleanup", "examples.iowa",
 )
 
 #: reference modules that are deliberately NOT rebuilt (out of scope) -> a clear error, not a stub
@@ -53,7 +53,6 @@ OUT_OF_SCOPE = {
     "models.human_player": "interactive play",
     "models.llm": "LLM clients",
     "examples.chess": "chess",
-    "examples.iowa": "the Iowa gambling task",
 }
 
 

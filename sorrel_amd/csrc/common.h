@@ -32,10 +32,14 @@ struct DevTables {
     // 16-bit counters, two channels per word (a sum over <= 7 layers of values <= 9 362 cannot carry), and the 256 possible results
     uint32_t delta16[2][SGW_MAX_TYPES];
     float post_lut[256];                                 // (float)(min(k, 255) / 255.0), k = 0 .. 255: what obs_finish returns for an integer sum
+    // drawn values (sgw_config.type_value_alt / value_alt_prob): read from global memory by the acts of worlds that have one, never staged in LDS
+    double value_alt[SGW_MAX_TYPES];
+    uint64_t alt_thr[SGW_MAX_TYPES];                     // floor(p * 2^32); 2^32 = always, 0 = the type does not draw
 };
 constexpr int kTabFastBytes = offsetof(DevTables, appearance);
+constexpr int kTabAllBytes = offsetof(DevTables, value_alt);   // what the general (non one-hot) kernels copy into LDS
 static_assert(kTabFastBytes % 16 == 0, "LDS table block must keep 16-byte alignment");
-static_assert(sizeof(DevTables) % 16 == 0, "LDS table block must keep 16-byte alignment");
+static_assert(kTabAllBytes % 16 == 0 && sizeof(DevTables) % 16 == 0, "LDS table block must keep 16-byte alignment");
 
 // What changes from turn to turn of a policy-driven loop, kept in device memory and advanced by the engine's own kernels
 // (sgw_turn_begin / sgw_turn_end) instead of arriving as kernel arguments: Environment.turn and the epoch, and for every agent
@@ -151,7 +155,30 @@ struct Params {
     // writes its observations / actions / rewards `t * ts_*` elements further on (0 = every turn overwrites the same tensors)
     uint32_t nturns;
     int64_t ts_obs, ts_act, ts_rew;
+    // Drawn values and the record of what each agent stepped on (SGW_AGENT_RULE_MOVE).  `extras` is the one word the acts test, wave-uniformly,
+    // so that a world without either pays a scalar compare per act: bit 0 = some type draws its value, bit 1 = target_types is bound
+    uint32_t extras;
+    uint32_t drawn_mask;       // types with value_alt_prob > 0
+    uint8_t* target_types;     // optional [E][A]: type id found on the target cell (255: invalid action / outside the grid)
 };
+constexpr uint32_t kExtraDrawn = 1u, kExtraTargets = 2u;
+// Who carries that code.  The instances the specialiser compiles for an engine have it compiled OUT (the uniform test cost the headline
+// 2 %: profiles/iowa_headline_ab.txt); an engine that draws values or keeps the record launches their `_x` twins (step_fast_x, step_big_x,
+// step_kernel_x, phase_rows_x: the same bodies with X = true), which exist in the specialiser's translation unit only.  The prebuilt instances
+// of the library -- the path without hipRTC -- take the wave-uniform test: no new axis in the prebuilt matrix.
+#ifdef SGW_JIT
+constexpr bool kExtrasDefault = false;
+#else
+constexpr bool kExtrasDefault = true;
+#endif
+// ... except the prebuilt step_fast instances with compile-time TABLES (the shipped examples' entity sets, the headline among them): compiled
+// out as well; an engine on one of them that binds the record gets the `_x` twin of that very instance from the specialiser.
+constexpr bool extras_default_tables(const int tc) { return kExtrasDefault && tc == 0; }
+template <bool XTRAS>
+__device__ __forceinline__ uint32_t extras_of(const Params& p) {
+    if constexpr (XTRAS) return p.extras;
+    else return 0u;
+}
 
 // ---------------------------------------------------------------- RNG
 struct U4 {
@@ -202,6 +229,17 @@ __device__ __forceinline__ uint32_t opaque(uint32_t v) {
 
 __device__ __forceinline__ uint32_t word_of(const U4& v, int i) {
     return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
+}
+
+// Drawn values: the u32 that decides what the entity on `cell` (layer-major cell index, the spawn stream's index) is worth in `turn`.
+// One draw per (cell, turn) is enough: the first agent that steps on a deck removes it (sorrel/examples/iowa/agents.py:47-60).
+__device__ __forceinline__ uint32_t value_draw(const Params& p, const uint32_t cell, const uint32_t turn, const uint32_t env_id, const uint32_t ep4) {
+    const U4 w = philox4x32_10(cell >> 2, turn, env_id, ep4 | SGW_STREAM_VALUE, p.seed_lo, p.seed_hi);
+    return word_of(w, (int)(cell & 3u));
+}
+// ... and the value itself (Deck.draw: the base payoff, or base + loss): `otherwise` is type_value[t]
+__device__ __forceinline__ double drawn_value(const DevTables* gtab, const uint32_t t, const uint32_t u, const double otherwise) {
+    return (uint64_t)u < gtab->alt_thr[t & 31u] ? gtab->value_alt[t & 31u] : otherwise;
 }
 
 // RGBObservationSpec: np.clip(obs, 0, 255) / 255 on the float64 layer sum (observation_spec.py:483)

@@ -91,6 +91,10 @@ __global__ __launch_bounds__(kBlock, 8) void phase_kernel(const Params p) {
     if (mover) {
         const bool tok = tinb && t < (uint32_t)p.T;
         val = tok ? wval[t & 31u] : 0.0;                                       // reward read BEFORE the move
+        if ((p.extras & kExtraDrawn) && tok && ((p.drawn_mask >> (t & 31u)) & 1u)) {   // a drawn value (common.h): wave-uniform, the turn is this launch's
+            const uint32_t turn_ = p.ts ? p.ts->turn + 1u : p.turn, ep4_ = (p.ts ? p.ts->epoch : p.epoch) << 4;
+            val = drawn_value(gtab, t, value_draw(p, (uint32_t)(p.zA * HW + ty * W + tx), turn_, p.first_env + (uint32_t)env, ep4_), val);
+        }
         const bool pass = tok && ((p.pass_mask >> (t & 31u)) & 1u);
         st |= !act_ok ? SGW_STATUS_BAD_ACTION : (!tinb ? SGW_STATUS_OOB_MOVE : (!tok ? SGW_STATUS_BAD_TYPE : 0));
         if (pass) {
@@ -110,6 +114,7 @@ __global__ __launch_bounds__(kBlock, 8) void phase_kernel(const Params p) {
                 reinterpret_cast<uint16_t*>(p.pos)[env * p.A + p.a0] = (uint16_t)new_pos;
             }
             p.rewards[env * p.A + p.a0] = (float)val;
+            if (p.target_types) p.target_types[env * p.A + p.a0] = (uint8_t)(tinb ? t : 255u);
             p.total[env] += val;                                               // float64, agent order (agent.py:172)
         }
     };
@@ -426,6 +431,7 @@ __device__ __forceinline__ int64_t read_action(const Params& p, const void* agen
     const uint64_t thr = ts ? ts->eps_thr[a] : 0ull;
     return (int64_t)argmax_explore(q, p.nact, thr, p.first_env + (uint32_t)env, ts ? ts->turn + 1u : 0u, ts ? ts->epoch << 4 : 0u, a, p.seed_lo, p.seed_hi);
 }
+template <bool XTRAS = kExtrasDefault>
 __device__ __forceinline__ int move_one(const Params& p, const DevTables* gtab, uint8_t* g, const int64_t env, const int a,
                                         const double* wval, const bool writer, MoveOut& mo, const ActIO io = ActIO{}) {
     const int H = p.H, W = p.W, HW = H * W;
@@ -464,7 +470,14 @@ __device__ __forceinline__ int move_one(const Params& p, const DevTables* gtab, 
             }
     }
     const bool tok = tinb && t < (uint32_t)p.T;
-    const double val = tok ? (wval ? wval[t & 31u] : gtab->value[t & 31u]) : 0.0;   // reward read BEFORE the move
+    double val = tok ? (wval ? wval[t & 31u] : gtab->value[t & 31u]) : 0.0;         // reward read BEFORE the move
+    if ((extras_of<XTRAS>(p) & kExtraDrawn) && tok && ((p.drawn_mask >> (t & 31u)) & 1u)) {
+        // a drawn value (common.h).  A phase of sgw_step carries its turn; sgw_act has none and reads the turn in flight from the device's turn
+        // state, which its caller keeps current with sgw_turn_set (as for SGW_ACT_QF32's exploration draw)
+        const TurnState* vts = io.ts ? io.ts : p.ts;
+        const uint32_t turn_ = vts ? vts->turn + 1u : p.turn, ep4_ = (vts ? vts->epoch : p.epoch) << 4;
+        val = drawn_value(gtab, t, value_draw(p, (uint32_t)(p.zA * HW + ty * W + tx), turn_, p.first_env + (uint32_t)env, ep4_), val);
+    }
     const bool pass = tok && ((p.pass_mask >> (t & 31u)) & 1u);
     st |= !act_ok ? SGW_STATUS_BAD_ACTION : (!tinb ? SGW_STATUS_OOB_MOVE : (!tok ? SGW_STATUS_BAD_TYPE : 0));
     mo.old_y = -1; mo.old_x = 0; mo.new_y = -1; mo.new_x = 0; mo.my_type = my_type; mo.found = t; mo.left = here;
@@ -477,6 +490,7 @@ __device__ __forceinline__ int move_one(const Params& p, const DevTables* gtab, 
             reinterpret_cast<uint16_t*>(p.pos)[env * p.A + a] = (uint16_t)((uint32_t)ty | ((uint32_t)tx << 8));
         }
         p.rewards[env * p.A + a] = (float)val;
+        if (extras_of<XTRAS>(p) & kExtraTargets) p.target_types[env * p.A + a] = (uint8_t)(tinb ? t : 255u);
         p.total[env] = tot + val;                                              // float64, agent order (agent.py:172)
         if (io.agent_action) p.actions[env * p.A + a] = (uint8_t)act;         // the record of what was taken
         if (io.reward_row) io.reward_row[env] = (float)val;
@@ -485,8 +499,8 @@ __device__ __forceinline__ int move_one(const Params& p, const DevTables* gtab, 
     return st;
 }
 
-template <int L, int NW, int R>
-__global__ __launch_bounds__(kBlock, 8) void phase_rows(const Params p) {
+template <int L, int NW, int R, bool XTRAS>
+__device__ __forceinline__ void phase_rows_body(const Params& p) {
     constexpr int V = 2 * R + 1, VV = V * V;
     constexpr int G = V <= 4 ? 4 : (V <= 8 ? 8 : 16);   // lanes per env; lane gl < V owns window row gl
     constexpr int EPW = 64 / G;                          // envs per wave
@@ -530,7 +544,7 @@ __global__ __launch_bounds__(kBlock, 8) void phase_rows(const Params p) {
     // ---- the move: decided from reads only; its stores wait for every row load of this wave
     gsync<1>();                                                                // table words visible to every lane
     MoveOut mo{-1, 0, -1, 0, 0u, 0u, 0u};
-    if (mover) st |= move_one(p, gtab, g, env, p.a0, wval, live && gl == 0, mo);
+    if (mover) st |= move_one<XTRAS>(p, gtab, g, env, p.a0, wval, live && gl == 0, mo);
     if (st && live && gl == 0) atomicOr(p.status, st);
     if (!render) return;
 
@@ -562,6 +576,18 @@ __global__ __launch_bounds__(kBlock, 8) void phase_rows(const Params p) {
 // agent's pov() reads at the start of a policy-driven turn (sorrel/agents/agent.py:167), rendered once; sgw_act then
 // repairs the cells that earlier agents' moves change.  Consecutive groups of a wave render consecutive agents of one
 // env (their rows share cache lines).
+template <int L, int NW, int R>
+__global__ __launch_bounds__(kBlock, 8) void phase_rows(const Params p) {
+    phase_rows_body<L, NW, R, kExtrasDefault>(p);
+}
+#ifdef SGW_JIT
+// the twin with drawn values / target_types compiled in (common.h: kExtrasDefault)
+template <int L, int NW, int R>
+__global__ __launch_bounds__(kBlock, 8) void phase_rows_x(const Params p) {
+    phase_rows_body<L, NW, R, true>(p);
+}
+#endif
+
 template <int L, int NW, int R>
 __global__ __launch_bounds__(kBlock, 8) void observe_rows(const Params p, const RowPtrs rp) {
     constexpr int V = 2 * R + 1, VV = V * V;

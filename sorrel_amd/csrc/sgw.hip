@@ -96,6 +96,8 @@ struct Kernel {
     const char* host_name = "-";
     std::string want;               // template-id of the specialised instance ("" : none wanted)
     hipFunction_t jit = nullptr;
+    hipFunction_t jit_x = nullptr;  // ... and its twin with drawn values / target_types compiled in (common.h: kExtrasDefault), when the engine needs it
+    bool tried_x = false;
     bool tried = false;             // the specialised instance has been asked for (and, if jit is still null, was refused)
     bool usable() const { return host != nullptr || !want.empty(); }
     const char* name() const { return (jit || (!host && !want.empty())) ? want.c_str() : host_name; }
@@ -263,6 +265,16 @@ int validate(const sgw_config* c) {
             return fail(SGW_EINVAL, "tag_it_type / tag_notit_type must be two distinct registered types");
         if (c->type_passable[c->tag_it_type] || c->type_passable[c->tag_notit_type])
             return fail(SGW_EINVAL, "tag agent types must be impassable");
+    }
+    for (int t = 0; t < c->num_types; ++t) {   // drawn values (sgw.h: type_value_alt / value_alt_prob)
+        if (!(c->value_alt_prob[t] >= 0.0 && c->value_alt_prob[t] <= 1.0))
+            return fail(SGW_EINVAL, "type %d: value_alt_prob must be in [0, 1]", t);
+        if (!std::isfinite(c->type_value_alt[t])) return fail(SGW_EINVAL, "type %d: type_value_alt must be finite", t);
+        if (c->value_alt_prob[t] == 0.0) continue;
+        if (c->agent_rule != SGW_AGENT_RULE_MOVE)
+            return fail(SGW_EINVAL, "type %d: a drawn value needs SGW_AGENT_RULE_MOVE (Tag ignores values, Cleanup sums every layer of the target)", t);
+        for (int a = 0; a < c->num_agents; ++a)
+            if (c->agent_type[a] == t) return fail(SGW_EINVAL, "type %d: an agent type cannot have a drawn value", t);
     }
     if (c->obs_post != SGW_OBS_POST_NONE && c->obs_post != SGW_OBS_POST_CLIP255_DIV255)
         return fail(SGW_EINVAL, "unknown obs_post %d", c->obs_post);
@@ -594,6 +606,8 @@ int plan_engine(sgw_engine* e, bool jit) {
         if (ones == 1 && !other) h.delta[ch >> 2][t] = 1u << (8 * (ch & 3));
         if (ones == 1 && !other && ch < 10) h.delta3[t] = 1u << (3 * ch);
         h.value[t] = c.type_value[t];
+        h.value_alt[t] = c.type_value_alt[t];
+        h.alt_thr[t] = prob_threshold(c.value_alt_prob[t]);
         h.thr_lo[t] = (uint32_t)(prob_threshold(c.spawn_prob[t]) & 0xFFFFFFFFull);
         h.spawn_count[t] = c.spawn_count[t];
         memcpy(h.spawn_choice[t], c.spawn_choice[t], SGW_MAX_CHOICES);
@@ -635,7 +649,7 @@ int plan_engine(sgw_engine* e, bool jit) {
     p.cells_pad = (p.cells + 15) & ~15;
     p.env_stride = c.grid_env_stride > 0 ? c.grid_env_stride : p.cells;
     p.env_lds = p.cells_pad + agent_lds_bytes(c.num_agents > 64 ? SGW_MAX_AGENTS : 64);      // (the generic kernel's per-agent LDS arrays: its AC template argument)
-    p.tab_bytes = onehot ? kTabFastBytes : (int)sizeof(DevTables);
+    p.tab_bytes = onehot ? kTabFastBytes : kTabAllBytes;
     p.default_type = (uint32_t)c.default_type;
     p.fill_type = (uint32_t)c.fill_type;
     for (int t = 0; t < c.num_types; ++t) {
@@ -644,7 +658,9 @@ int plan_engine(sgw_engine* e, bool jit) {
             if (prob_threshold(c.spawn_prob[t]) >= 4294967296ull) p.thr_full_mask |= 1u << t;
         }
         if (c.type_passable[t]) p.pass_mask |= 1u << t;
+        if (h.alt_thr[t]) p.drawn_mask |= 1u << t;
     }
+    p.extras = p.drawn_mask ? kExtraDrawn : 0u;
     for (int a = 0; a < c.num_actions; ++a) {
         p.dy_pack |= (uint32_t)(c.action_dy[a] + 1) << (2 * a);
         p.dx_pack |= (uint32_t)(c.action_dx[a] + 1) << (2 * a);
@@ -1046,11 +1062,54 @@ int resolve_kernel(sgw_engine* e, Kernel& k) {
     return SGW_OK;
 }
 
+// Specialised instances carry no code for drawn values / target_types (common.h: kExtrasDefault), nor do the prebuilt step_fast instances with
+// compile-time tables; the kernels that act have a twin that does, compiled by the specialiser.  "" : `k` serves the extras itself (a prebuilt
+// instance with the wave-uniform test) or nobody acts in it.
+std::string extras_twin_name(const Kernel& k) {
+    std::string src;
+    if (k.jit) src = k.want;
+    else if (k.host && strncmp(k.host_name, "step_fast<", 10) == 0) {
+        // template arguments: ONEHOT, TL, TC, ...: TC != 0 = compile-time tables
+        const char* c1 = strchr(k.host_name, ',');
+        const char* c2 = c1 ? strchr(c1 + 1, ',') : nullptr;
+        if (c2 && atoi(c2 + 1) != 0) src = k.host_name;
+    }
+    for (const char* base : {"step_fast<", "step_big<", "step_kernel<", "phase_rows<"}) {
+        const size_t n = strlen(base);
+        if (src.compare(0, n, base) == 0) return src.substr(0, n - 1) + "_x" + src.substr(n - 1);
+    }
+    return std::string();
+}
+int resolve_twin(sgw_engine* e, Kernel& k) {
+    if (k.jit_x) return SGW_OK;
+    const std::string name = extras_twin_name(k);
+    if (name.empty()) return SGW_OK;
+    if (k.tried_x) return fail(SGW_EHIP, "no instance of %s is available", name.c_str());
+    k.tried_x = true;
+    std::string err;
+    k.jit_x = jit_get(name, e->opt, e->arch.c_str(), e->dev, &err);
+    if (!k.jit_x) return fail(SGW_EHIP, "specialising %s failed: %s", name.c_str(), err.c_str());   // (a missing kernel is an error, not a silent constant reward)
+    if (std::max(e->lds_bytes, e->step_lds_bytes) > 65536)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.jit_x), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(e->lds_bytes, e->step_lds_bytes) + 16);
+    return SGW_OK;
+}
+// ... for every instance the engine holds: at sgw_create / sgw_bind_target_types, so that no stream-ordered call compiles
+int resolve_twins(sgw_engine* e) {
+    for (Kernel* k : {&e->k_step, &e->k_plain, &e->k_multi, &e->k_walk, &e->k_rows})
+        if (int rc = resolve_twin(e, *k)) return rc;
+    return SGW_OK;
+}
+
 int launch_kernel(sgw_engine* e, Kernel& k, unsigned blocks, unsigned threads, size_t lds, hipStream_t s, Params& p, RowPtrs* rp) {
     if (!k.jit && !k.want.empty() && !k.tried)
         if (int rc = resolve_kernel(e, k)) return rc;
     static RowPtrs no_rows{};                 // (kernels that take the row pointers read them only when Params says so: rows_on, ...)
     void* args[2] = {&p, rp ? rp : &no_rows};
+    if (p.extras && p.do_move && !extras_twin_name(k).empty()) {
+        if (int rc = resolve_twin(e, k)) return rc;       // (an instance resolved late, e.g. the turn loop of sgw_rollout: its twin follows now)
+        HIP_TRY(hipModuleLaunchKernel(k.jit_x, blocks, 1, 1, threads, 1, 1, (unsigned)lds, s, args, nullptr));
+        return SGW_OK;
+    }
     if (k.jit) HIP_TRY(hipModuleLaunchKernel(k.jit, blocks, 1, 1, threads, 1, 1, (unsigned)lds, s, args, nullptr));
     else if (k.host) HIP_TRY(hipLaunchKernel(k.host, dim3(blocks), dim3(threads), args, lds, s));
     else return fail(SGW_EHIP, "no kernel to launch");
@@ -1099,7 +1158,7 @@ int sgw_debug_stamps(unsigned long long* out) {   // diagnostic builds only; not
 }
 #endif
 
-const char* sgw_version(void) { return "sgw 0.2 (gfx950)"; }
+const char* sgw_version(void) { return "sgw 0.3 (gfx950)"; }
 
 int64_t sgw_obs_elems_per_env(const sgw_config* c) {
     const int64_t V = 2 * c->vision_radius + 1;
@@ -1319,6 +1378,8 @@ int sgw_create(const sgw_config* cfg, sgw_engine** out) {
             return fail(SGW_EHIP, "cannot reserve %zu bytes of LDS: %s", e->lds_bytes, hipGetErrorString(err));
         }
     }
+    if (e->base.extras)
+        if (int rc = resolve_twins(e)) { sgw_destroy(e); return rc; }
     *out = e;
     return SGW_OK;
 }
@@ -1598,6 +1659,7 @@ int sgw_capabilities(sgw_engine* e) {
     {   // sgw_turn_resolve: plain movers with impassable agent types, float32 windows
         bool ok = e->cfg.agent_rule == SGW_AGENT_RULE_MOVE && e->obs_format == SGW_OBS_F32 && e->cfg.num_agents <= 64;   // (the resolve kernel keeps an agent per lane)
         for (int a = 0; a < e->cfg.num_agents; ++a) ok = ok && !e->cfg.type_passable[e->cfg.agent_type[a]];
+        ok = ok && !e->base.drawn_mask;   // (a drawn value: the commit of sgw_turn_resolve knows no turn -- such worlds take the sequential turn)
         if (ok) caps |= SGW_CAP_RESOLVE;
     }
     if (e->big) caps |= SGW_CAP_OBS_AGENT_MAJOR;
@@ -1717,7 +1779,7 @@ static int act_impl(sgw_engine* e, uint8_t* grid, uint8_t* agent_pos, uint8_t* a
         return fail(SGW_EINVAL, "sgw_act: SGW_ACT_QF32 action values must be 4-byte aligned");
     rp.agent_action = agent_action; rp.action_kind = action_kind; rp.reward_row = reward_row; rp.action_row = action_row;
     rp.ts = ts;
-    rp.ets = (agent_action && action_kind == SGW_ACT_QF32) ? e->d_turn : nullptr;
+    rp.ets = ((agent_action && action_kind == SGW_ACT_QF32) || e->base.drawn_mask) ? e->d_turn : nullptr;   // (a drawn value is keyed by the turn in flight, too)
     rp.dual = (dual && ts && e->turn_rows) ? 1 : 0;
     Params p = e->base;
     p.grid = grid; p.pos = agent_pos; p.actions = actions; p.rewards = rewards; p.total = total_reward;
@@ -2090,6 +2152,18 @@ int sgw_bind_row_tail(sgw_engine* e, int kind, int tail_len, const float* table)
     if (tail_len < 1 || tail_len > 4096 || !table) return fail(SGW_EINVAL, "SGW_TAIL_POSITION_TABLE needs a device table of [H][W][tail_len] floats, 1 <= tail_len <= 4096");
     e->tail_kind = kind; e->tail_len = tail_len; e->tail_table = table;
     tail_twin();
+    return SGW_OK;
+}
+
+int sgw_bind_target_types(sgw_engine* e, uint8_t* target_types) {
+    if (!e) return fail(SGW_EINVAL, "sgw_bind_target_types: NULL engine");
+    if (target_types && e->cfg.agent_rule != SGW_AGENT_RULE_MOVE)
+        return fail(SGW_EINVAL, "sgw_bind_target_types: the record is kept by the acts of SGW_AGENT_RULE_MOVE");
+    if (target_types)
+        if (int rc = resolve_twins(e)) return rc;
+    // kept in the launch parameters every call starts from: every act sees it, and an unbound engine launches what it launched before
+    e->base.target_types = target_types;
+    e->base.extras = (e->base.extras & ~kExtraTargets) | (target_types ? kExtraTargets : 0u);
     return SGW_OK;
 }
 

@@ -62,8 +62,8 @@ constexpr int big_agent_lds(bool tag) { return kBigAgentLds + (tag ? kBigTagLds 
 // ROWS (round 6): the instance behind sgw_sweep_observe_rows -- agent a's window of env e goes to rp.p[a] + e * rp.stride (its own row, e.g. of its replay buffer),
 // followed by the bound row tail; a separate instantiation (specialised in-process only): in the ordinary instances the extra addressing cost the walking variant
 // 37 spilled scalars and 8 bytes of scratch per lane.  Every instance takes the row pointers as its second argument (read by ROWS instances only).
-template <bool ONEHOT, int TL, int TC, int TR, bool MULTI = false, bool WALK = false, bool TAG = false, int BT = kBigThreads, bool ROWS = false>
-__global__ __launch_bounds__(BT, WALK ? SGW_WALK_WAVES : (MULTI ? 6 : SGW_BIG_WAVES)) void step_big(const Params p, [[maybe_unused]] const RowPtrs rp) {
+template <bool ONEHOT, int TL, int TC, int TR, bool MULTI, bool WALK, bool TAG, int BT, bool ROWS, bool XTRAS>
+__device__ __forceinline__ void step_big_body(const Params& p, [[maybe_unused]] const RowPtrs& rp) {
     static_assert(!ROWS || (!MULTI && !WALK), "ROWS: the plain single-turn variant");
     constexpr int kBT = BT, kBW = BT / 64;   // threads / waves of this instance
     static_assert(!(MULTI && WALK), "a rollout keeps one env per workgroup");
@@ -417,6 +417,16 @@ __global__ __launch_bounds__(BT, WALK ? SGW_WALK_WAVES : (MULTI ? 6 : SGW_BIG_WA
         }
         double val = __shfl(vtab, (int)(jr & 31u));                     // reward = value of the target BEFORE the move
         if (!(jr & 0x100u)) val = 0.0;
+        if constexpr (!TAG) {
+            if (const uint32_t xtr = extras_of<XTRAS>(p)) {       // uniform (a kernel argument): drawn values and the record of what each agent found (common.h)
+                if ((xtr & kExtraDrawn) && mine && (jr & 0x100u) && ((p.drawn_mask >> (jr & 31u)) & 1u)) {
+                    // lane = agent: each draws for its own target cell (layer-major index; ta_v counts LDS rows of pitch P)
+                    const uint32_t cell = ((uint32_t)p.zA * (uint32_t)H + (npos_v & 0xFFu)) * (uint32_t)W + (npos_v >> 8);
+                    val = drawn_value(gtab, jr & 31u, value_draw(p, cell, turn, env_id, ep4), val);
+                }
+                if (mine && (xtr & kExtraTargets)) p.target_types[env * p.A + tid] = (uint8_t)(validv ? (jr & 0xFFu) : 255u);
+            }
+        }
         if constexpr (TAG) {
             // TagAgent.act: reward_per_turn for not being "it" once its own act is over (agents.py:100-106)
             const uint32_t after = tagj ? p.tag_notit : pov_v;
@@ -733,3 +743,14 @@ __global__ __launch_bounds__(BT, WALK ? SGW_WALK_WAVES : (MULTI ? 6 : SGW_BIG_WA
     if (tid0 < 64 && st_lane) atomicOr(p.status, st_lane);
 }
 
+template <bool ONEHOT, int TL, int TC, int TR, bool MULTI = false, bool WALK = false, bool TAG = false, int BT = kBigThreads, bool ROWS = false>
+__global__ __launch_bounds__(BT, WALK ? SGW_WALK_WAVES : (MULTI ? 6 : SGW_BIG_WAVES)) void step_big(const Params p, const RowPtrs rp) {
+    step_big_body<ONEHOT, TL, TC, TR, MULTI, WALK, TAG, BT, ROWS, kExtrasDefault>(p, rp);
+}
+#ifdef SGW_JIT
+// the twin with drawn values / target_types compiled in (common.h: kExtrasDefault)
+template <bool ONEHOT, int TL, int TC, int TR, bool MULTI = false, bool WALK = false, bool TAG = false, int BT = kBigThreads, bool ROWS = false>
+__global__ __launch_bounds__(BT, WALK ? SGW_WALK_WAVES : (MULTI ? 6 : SGW_BIG_WAVES)) void step_big_x(const Params p, const RowPtrs rp) {
+    step_big_body<ONEHOT, TL, TC, TR, MULTI, WALK, TAG, BT, ROWS, true>(p, rp);
+}
+#endif

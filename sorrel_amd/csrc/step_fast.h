@@ -213,7 +213,7 @@ __device__ __forceinline__ void fast_rows_emit(const Params& p, const RowPtrs* r
 // ROWX (round 6): the same call on the instances that stage CHUNKS of agents (STAGE: layered rule sets -- Cleanup --, Tag, run-time maps and tables): the host
 // launches with one agent per chunk, and a chunk leaves for its agent's own row -- emit_chunk's line-aligned 16-byte streaming stores, the staging offset
 // taken from the ROW's address -- followed by the bound row tail (TagAgent.pov's flag, CleanupObservation's positional code).
-template <bool ONEHOT, int TL, int TC, int TR, int TH, int TW, bool TAG, bool RULES, bool STAGE, bool MULTI, bool P3, bool I16, bool ROWS, bool ROWX = false, bool TAIL = false>
+template <bool ONEHOT, int TL, int TC, int TR, int TH, int TW, bool TAG, bool RULES, bool STAGE, bool MULTI, bool P3, bool I16, bool ROWS, bool ROWX = false, bool TAIL = false, bool XTRAS = kExtrasDefault>
 __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] const RowPtrs* rp) {
     static_assert(!ROWS || (ONEHOT && TL && TC && TH && TW && !RULES && !STAGE && !MULTI && !P3 && !I16), "ROWS: plain or Tag movers, one-hot, compile-time shape");
     static_assert(!ROWX || (ONEHOT && STAGE && !MULTI && !I16 && !ROWS), "ROWX: a chunk-staging single-turn instance");
@@ -523,6 +523,13 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             st_lane |= !act_ok ? SGW_STATUS_BAD_ACTION : (!inb ? SGW_STATUS_OOB_MOVE : 0);
         }
         oaddr_v = (uint32_t)zoff + py * (uint32_t)W + px;   // own cell
+        // Drawn values (sgw_config.value_alt_prob): lane a's u32 for ITS target cell, drawn in parallel next to the action draw -- the cell is
+        // known before the sequential resolve (only the agent itself moves it), what it holds is not.  The same register then takes the record of
+        // what the agent found there (target_types): iteration a consumes lane a's draw and is the one that writes lane a's record.
+        uint32_t xv = 255u;
+        if (extras_of<XTRAS>(p) & kExtraDrawn) {      // wave-uniform: a world without a drawn value skips the Philox block
+            if (taddr_v != 0xFFFFFFFFu) xv = value_draw(p, taddr_v, turn, env_id, ep4);   // (the LDS byte offset of a cell IS its layer-major index)
+        }
         rew_bits = 0;
         moved = 0;
         const int64_t turn_obs = tix * p.ts_obs;   // this turn's observation slot (elements)
@@ -771,9 +778,21 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)lg[valid ? s_t : (uint32_t)s_o]);
             const bool tok = valid && t < (uint32_t)p.T;
             const uint32_t tl = t & 31u;
-            const uint32_t v_lo = (uint32_t)__builtin_amdgcn_readlane((int)vt_lo, (int)tl);
-            const uint32_t v_hi = (uint32_t)__builtin_amdgcn_readlane((int)vt_hi, (int)tl);
-            const uint32_t v_f = (uint32_t)__builtin_amdgcn_readlane((int)vt_f32, (int)tl);
+            uint32_t v_lo = (uint32_t)__builtin_amdgcn_readlane((int)vt_lo, (int)tl);
+            uint32_t v_hi = (uint32_t)__builtin_amdgcn_readlane((int)vt_hi, (int)tl);
+            uint32_t v_f = (uint32_t)__builtin_amdgcn_readlane((int)vt_f32, (int)tl);
+            if constexpr (!TAG) {
+                if (extras_of<XTRAS>(p)) {                // wave-uniform (a kernel argument): worlds without a drawn value or a bound record pay this test only
+                    if (tok && ((p.drawn_mask >> tl) & 1u)) {   // the type found draws: its other value when the cell's u32 is below the type's threshold
+                        const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)xv, a);
+                        const double dv = drawn_value(gtab, tl, u, __longlong_as_double(((long long)v_hi << 32) | v_lo));
+                        v_lo = (uint32_t)__double_as_longlong(dv);
+                        v_hi = (uint32_t)(__double_as_longlong(dv) >> 32);
+                        v_f = __float_as_uint((float)dv);       // the float32 reward is the rounding of the double the total adds
+                    }
+                    xv = lane == a ? (valid ? t : 255u) : xv;   // what world.observe(new_location) returned
+                }
+            }
             const bool pass = tok && ((p.pass_mask >> tl) & 1u);
             if (pass && lane == 0) {
                 lg[s_t] = (uint8_t)my_type;
@@ -867,6 +886,8 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
         }
         if (p.do_move && mine) {      // this turn's rewards (and what TagAgent.pov appends)
             p.rewards[tix * p.ts_rew + env * p.A + lane] = __uint_as_float(rew_bits);
+            if constexpr (!TAG)
+                if (extras_of<XTRAS>(p) & kExtraTargets) p.target_types[env * p.A + lane] = (uint8_t)xv;   // (a rollout's turns overwrite each other: the last one stays)
             if (p.state_at_pov) p.state_at_pov[env * p.A + lane] = (uint8_t)pov_type;
         }
         if (tix + 1 < nturns) yx = moved ? npos : yx;   // the next turn starts where this one ended
@@ -919,17 +940,24 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
 
 template <bool ONEHOT, int TL, int TC, int TR, int TH, int TW, bool TAG = false, bool RULES = false, bool STAGE = false, bool MULTI = false, bool P3 = false, bool I16 = false>
 __global__ __launch_bounds__(kBlock, MULTI ? SGW_FAST_MULTI_WAVES : (RULES ? (STAGE ? 7 : SGW_FAST_RULES_PLAIN_WAVES) : 8)) void step_fast(const Params p) {
-    step_fast_body<ONEHOT, TL, TC, TR, TH, TW, TAG, RULES, STAGE, MULTI, P3, I16, false>(p, nullptr);
+    step_fast_body<ONEHOT, TL, TC, TR, TH, TW, TAG, RULES, STAGE, MULTI, P3, I16, false, false, false, extras_default_tables(TC)>(p, nullptr);
 }
+#ifdef SGW_JIT
+// the twin with drawn values / target_types compiled in (common.h: kExtrasDefault)
+template <bool ONEHOT, int TL, int TC, int TR, int TH, int TW, bool TAG = false, bool RULES = false, bool STAGE = false, bool MULTI = false, bool P3 = false, bool I16 = false>
+__global__ __launch_bounds__(kBlock, MULTI ? SGW_FAST_MULTI_WAVES : (RULES ? (STAGE ? 7 : SGW_FAST_RULES_PLAIN_WAVES) : 8)) void step_fast_x(const Params p) {
+    step_fast_body<ONEHOT, TL, TC, TR, TH, TW, TAG, RULES, STAGE, MULTI, P3, I16, false, false, false, true>(p, nullptr);
+}
+#endif
 
 // ... on the chunk-staging instances (ROWX; specialised in-process only: the library holds no prebuilt twin)
 template <int TL, int TC, int TR, int TH, int TW, bool TAG, bool RULES, bool P3>
 __global__ __launch_bounds__(kBlock, RULES ? 7 : 8) void step_fast_rowsx(const Params p, const RowPtrs rp) {
-    step_fast_body<true, TL, TC, TR, TH, TW, TAG, RULES, true, false, P3, false, false, true>(p, &rp);
+    step_fast_body<true, TL, TC, TR, TH, TW, TAG, RULES, true, false, P3, false, false, true, false, false>(p, &rp);   // (nobody acts in a rows launch)
 }
 
 // sweep + every agent's window into per-agent rows (sgw_sweep_observe_rows): nobody acts in this launch
 template <int TL, int TC, int TR, int TH, int TW, bool TAG = false, bool TAIL = false>
 __global__ __launch_bounds__(kBlock, 8) void step_fast_rows(const Params p, const RowPtrs rp) {
-    step_fast_body<true, TL, TC, TR, TH, TW, TAG, false, false, false, false, false, true, false, TAIL>(p, &rp);
+    step_fast_body<true, TL, TC, TR, TH, TW, TAG, false, false, false, false, false, true, false, TAIL, false>(p, &rp);
 }

@@ -27,8 +27,8 @@ __host__ __device__ constexpr int agent_lds_bytes(int cap) { return 10 * cap + 1
 // ROWS (round 6): the instance behind sgw_sweep_observe_rows on the worlds this kernel serves (small worlds packed two or four to a wave, rule worlds above 8 KiB,
 // more than 64 agents) -- agent a's window of env e goes to rp.p[a] + e * rp.stride, the bound row tail behind it; specialised in-process only.  Every instance
 // takes the row pointers as its second argument (read by ROWS instances only).
-template <int G, bool ONEHOT, int TL = 0, int TC = 0, int RULE = SGW_AGENT_RULE_MOVE, int TR = 0, int TH = 0, int TW = 0, bool MULTI = false, int AC = 64, bool ROWS = false>
-__global__ __launch_bounds__(kBlock, SGW_GENERIC_WAVES) void step_kernel(const Params p, [[maybe_unused]] const RowPtrs rp) {
+template <int G, bool ONEHOT, int TL, int TC, int RULE, int TR, int TH, int TW, bool MULTI, int AC, bool ROWS, bool XTRAS>
+__device__ __forceinline__ void step_kernel_body(const Params& p, [[maybe_unused]] const RowPtrs& rp) {
     static_assert(AC == 64 || (AC == SGW_MAX_AGENTS && G == 256), "more than 64 agents: the workgroup-per-env instances");
     static_assert(!ROWS || !MULTI, "ROWS: a single-turn instance");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -306,6 +306,13 @@ __global__ __launch_bounds__(kBlock, SGW_GENERIC_WAVES) void step_kernel(const P
                 const uint32_t t = inb ? lg[taddr] : 0xFFu;
                 const bool tok = t < (uint32_t)p.T;
                 double val = (inb && tok && RULE == SGW_AGENT_RULE_MOVE) ? tab->value[t & 31u] : 0.0;   // reward read BEFORE the move
+                if constexpr (RULE == SGW_AGENT_RULE_MOVE) {
+                    if (const uint32_t xtr = extras_of<XTRAS>(p)) {   // uniform (a kernel argument): drawn values and the record of what the agent found (common.h); every thread draws the same word
+                        if ((xtr & kExtraDrawn) && inb && tok && ((p.drawn_mask >> (t & 31u)) & 1u))
+                            val = drawn_value(p.tab, t, value_draw(p, (uint32_t)taddr, turn, env_id, ep4), val);
+                        if (gtid == 0 && (xtr & kExtraTargets)) p.target_types[env * p.A + a] = (uint8_t)(inb ? t : 255u);
+                    }
+                }
                 const bool pass = inb && tok && ((p.pass_mask >> (t & 31u)) & 1u);
                 const int cy = pass ? ty : y, cx = pass ? tx : x;   // where the agent stands after the move
                 gsync<WPE>();   // every thread has read s_type / the target before thread 0 rewrites them
@@ -606,6 +613,13 @@ __global__ __launch_bounds__(kBlock, SGW_GENERIC_WAVES) void step_kernel(const P
                 const uint32_t t = inb ? lg[taddr] : 0xFFu;
                 const bool tok = t < (uint32_t)p.T;
                 double val = (inb && tok && RULE == SGW_AGENT_RULE_MOVE) ? tab->value[t & 31u] : 0.0;   // reward read BEFORE the move
+                if constexpr (RULE == SGW_AGENT_RULE_MOVE) {
+                    if (const uint32_t xtr = extras_of<XTRAS>(p)) {   // uniform (a kernel argument): drawn values and the record of what the agent found (common.h); every thread draws the same word
+                        if ((xtr & kExtraDrawn) && inb && tok && ((p.drawn_mask >> (t & 31u)) & 1u))
+                            val = drawn_value(p.tab, t, value_draw(p, (uint32_t)taddr, turn, env_id, ep4), val);
+                        if (atid == 0 && (xtr & kExtraTargets)) p.target_types[env * p.A + a] = (uint8_t)(inb ? t : 255u);
+                    }
+                }
                 const bool pass = inb && tok && ((p.pass_mask >> (t & 31u)) & 1u);
                 const int cy = pass ? ty : y, cx = pass ? tx : x;   // where the agent stands after the move
                 gsync<WPA>();   // every thread has read s_type / the target before thread 0 rewrites them
@@ -692,3 +706,14 @@ __global__ __launch_bounds__(kBlock, SGW_GENERIC_WAVES) void step_kernel(const P
     }
 }
 
+template <int G, bool ONEHOT, int TL = 0, int TC = 0, int RULE = SGW_AGENT_RULE_MOVE, int TR = 0, int TH = 0, int TW = 0, bool MULTI = false, int AC = 64, bool ROWS = false>
+__global__ __launch_bounds__(kBlock, SGW_GENERIC_WAVES) void step_kernel(const Params p, const RowPtrs rp) {
+    step_kernel_body<G, ONEHOT, TL, TC, RULE, TR, TH, TW, MULTI, AC, ROWS, kExtrasDefault>(p, rp);
+}
+#ifdef SGW_JIT
+// the twin with drawn values / target_types compiled in (common.h: kExtrasDefault)
+template <int G, bool ONEHOT, int TL = 0, int TC = 0, int RULE = SGW_AGENT_RULE_MOVE, int TR = 0, int TH = 0, int TW = 0, bool MULTI = false, int AC = 64, bool ROWS = false>
+__global__ __launch_bounds__(kBlock, SGW_GENERIC_WAVES) void step_kernel_x(const Params p, const RowPtrs rp) {
+    step_kernel_body<G, ONEHOT, TL, TC, RULE, TR, TH, TW, MULTI, AC, ROWS, true>(p, rp);
+}
+#endif

@@ -128,6 +128,28 @@ class GridEngine:
                 raise ValueError("agent_dir must be contiguous uint8 [E, A] on the engine's device")
             N.check(self._lib.sgw_bind_agent_dir(self._h, self._ptr(self.agent_dir)))
 
+        # what every agent stepped on this turn (uint8 [E, A]; N.NO_TARGET: invalid action / outside the grid): on request only
+        self.target_types = None
+        if tensors.get("target_types") is not None:
+            self.bind_target_types(tensors["target_types"])
+
+    def bind_target_types(self, t=True):
+        """``sgw_bind_target_types``: from now on every act of a plain mover records the entity type it found on its target cell in
+        ``self.target_types`` (uint8 ``[E, A]``; ``N.NO_TARGET`` for an invalid action or a target outside the grid) -- what
+        ``GamblingAgent.act`` counts as an encounter.  ``t``: True allocates the tensor, a tensor adopts it, None / False unbinds."""
+        E, A = self.num_envs, self.spec.num_agents
+        if t is None or t is False:
+            N.check(self._lib.sgw_bind_target_types(self._h, None))
+            self.target_types = None
+            return None
+        if t is True:
+            t = self.target_types if self.target_types is not None else torch.full((E, A), N.NO_TARGET, dtype=torch.uint8, device=self.device)
+        if tuple(t.shape) != (E, A) or t.dtype != torch.uint8 or t.device != self.device or not t.is_contiguous():
+            raise ValueError("target_types must be contiguous uint8 [E, A] on the engine's device")
+        N.check(self._lib.sgw_bind_target_types(self._h, self._ptr(t)))
+        self.target_types = t
+        return t
+
     # ------------------------------------------------------------------ util
     def _stream(self):
         """The caller's current stream on the engine's device (raw handle; the private fast accessor PyTorch's own

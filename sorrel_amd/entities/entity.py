@@ -4,7 +4,7 @@ from __future__ import annotations
 from pathlib import Path
 from typing import Optional
 
-from sorrel_amd.entities.rules import TransitionRule
+from sorrel_amd.entities.rules import TransitionRule, ValueRule
 
 
 class Entity:
@@ -18,7 +18,9 @@ class Entity:
     Batched-engine addition: ``transition_rule`` -- the declarative form of
     ``transition()`` (see ``sorrel_amd.entities.rules``).  In the batched world a
     cell stores an entity *type* id; two entities are the same type when class,
-    kind, value, passable, has_transitions and rule all agree.
+    kind, value, passable, has_transitions and rule all agree.  ``value_rule`` -- the
+    declarative form of a value that is redrawn every turn (``rules.DrawnValue``); it is
+    part of the type, and ``value`` then holds the rule's ``otherwise`` outcome.
     """
 
     _location: Optional[tuple]
@@ -28,6 +30,7 @@ class Entity:
     kind: str
     sprite: Path
     transition_rule: Optional[TransitionRule] = None
+    value_rule: Optional[ValueRule] = None
 
     def __init__(self):
         self._location = None
@@ -61,5 +64,10 @@ class Entity:
     # ------------------------------------------------------------------ batched engine
     def type_key(self):
         rule = self.transition_rule if self.has_transitions else None
-        return (type(self).__module__, type(self).__qualname__, self.kind, float(self.value), bool(self.passable),
-                bool(self.has_transitions), id(rule) if rule is not None else None)
+        if callable(self.value):
+            raise ValueError(f"{type(self).__name__}.value is a callable; a value that changes from turn to turn is declared "
+                             "with value_rule (sorrel_amd.entities.rules.DrawnValue)")
+        key = (type(self).__module__, type(self).__qualname__, self.kind, float(self.value), bool(self.passable),
+               bool(self.has_transitions), id(rule) if rule is not None else None)
+        vrule = self.value_rule
+        return key if vrule is None else key + (vrule.key(),)

@@ -91,3 +91,44 @@ class AgeRule(TransitionRule):
                 rules.append(rule)
             self._chains[key] = list(zip(stages, rules))
         return self._chains[key]
+
+
+class ValueRule:
+    """Base class of the declarative ``Entity.value`` rules: what an entity is worth when its value is not one constant."""
+
+
+class DrawnValue(ValueRule):
+    """The entity's value is redrawn every turn between two outcomes: ``alt`` with probability ``prob``, else ``otherwise`` --
+    the Iowa Gambling Task's ``Deck.transition`` (``sorrel/examples/iowa/entities.py:45-70``: a base payoff, plus a loss with
+    probability 0.5 or 0.1).  Set it as ``value_rule`` on an entity class or instance.
+
+    On the device nothing is stored per cell: the draw is a function of (seed, env, epoch, turn, cell) on the engine's counter
+    RNG (stream ``SGW_STREAM_VALUE``), made when an agent steps on the cell.  The host-side ``.value`` of such an entity stays
+    its ``otherwise`` value; the per-turn draw is visible through the rewards only.  Two outcomes are what the engine runs:
+    callables and longer outcome lists are rejected when the engine is compiled."""
+
+    def __init__(self, otherwise, alt, prob):
+        self.otherwise, self.alt, self.prob = otherwise, alt, prob
+
+    def resolve(self):
+        """(otherwise, alt, prob) as floats, or ``ValueError`` for what a device cannot run."""
+        import math
+
+        for name in ("otherwise", "alt", "prob"):
+            v = getattr(self, name)
+            if callable(v):
+                raise ValueError(f"DrawnValue.{name} is a callable; the device draws between two constants")
+            if isinstance(v, (list, tuple, dict)) or hasattr(v, "__len__"):
+                raise ValueError(f"DrawnValue.{name} must be one number (two outcomes per entity type are what the engine runs)")
+        o, a, p = float(self.otherwise), float(self.alt), float(self.prob)
+        if not (math.isfinite(o) and math.isfinite(a)):
+            raise ValueError("DrawnValue outcomes must be finite")
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("DrawnValue.prob must be in [0, 1]")
+        return o, a, p
+
+    def key(self):
+        try:
+            return ("DrawnValue",) + self.resolve()
+        except (ValueError, TypeError):
+            return ("DrawnValue", id(self))

@@ -256,13 +256,32 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
         def kind_mask(kinds_):
             return sum(1 << t for t, p in enumerate(protos) if p.kind in kinds_)
 
+        # value rules: a value redrawn every turn between two outcomes (rules.DrawnValue)
+        from sorrel_amd.entities.rules import DrawnValue, ValueRule
+        values, value_alt, alt_prob = [], [0.0] * T, [0.0] * T
+        for t, p in enumerate(protos):
+            vrule = getattr(p, "value_rule", None)
+            if callable(p.value):
+                raise ValueError(f"{type(p).__name__}.value is a callable; declare a value that changes from turn to turn with value_rule")
+            if vrule is None:
+                values.append(p.value)
+                continue
+            if not isinstance(vrule, DrawnValue):
+                raise ValueError(f"{type(p).__name__}: unsupported value rule {vrule!r}; the device draws between two constants (DrawnValue)")
+            if isinstance(p, Agent):
+                raise ValueError(f"{type(p).__name__}: an agent cannot have a drawn value")
+            if extra["agent_rule"] != 0:
+                raise ValueError(f"{type(p).__name__}: drawn values need plain movers (Tag ignores values, Cleanup sums every layer of the target)")
+            o, a_, pr = vrule.resolve()
+            values.append(o)
+            value_alt[t], alt_prob[t] = a_, pr
         lay = w.layout or dict(fill=[w.default_type] * w.layers, border=[NO_BORDER] * w.layers, dense_prob=0.0, dense=[])
         return WorldSpec(
             height=w.height, width=w.width, layers=w.layers, num_agents=len(agents),
             vision_radius=0 if ospec.full_view else ospec.vision_radius, num_channels=C, agent_layer=w.agent_layer,
             default_type=w.default_type, fill_type=fill_type, action_dy=dy, action_dx=dx,
             agent_type=agent_types,
-            type_value=[p.value for p in protos], type_passable=[1 if p.passable else 0 for p in protos],
+            type_value=values, type_value_alt=value_alt, value_alt_prob=alt_prob, type_passable=[1 if p.passable else 0 for p in protos],
             type_rule=[RULE_SPAWN if t in spawn else RULE_BECOME_IF if t in become else RULE_NONE for t in range(T)],
             rule_layer=[become[t][1] if t in become else 0 for t in range(T)],
             rule_mask=[kind_mask(become[t][2]) if t in become else 0 for t in range(T)],
@@ -303,6 +322,11 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
             tensors["agent_state"] = w.agent_state          # survives engine rebuilds (and resets)
         if getattr(w, "agent_dir", None) is not None:
             tensors["agent_dir"] = w.agent_dir
+        if self.record_targets:                               # what every agent stepped on (sgw_bind_target_types): one tensor, every handle
+            tt = getattr(w, "target_types", None)
+            if tt is None or tuple(tt.shape) != (w.num_envs, len(self.agents)):
+                tt = torch.full((w.num_envs, len(self.agents)), 255, dtype=torch.uint8, device=w.device)
+            w.target_types = tensors["target_types"] = tt
         # agents that differ, or whose own spec is the whole map, step one after another on their own handles (take_turn); no handle
         # then needs the [E][A][C][V][V] tensor of a fused turn
         self._mixed = len(distinct) > 1 or any(a.observation_spec.full_view for a in self.agents)
@@ -369,6 +393,22 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
     #: that branches on host state must stay eager).
     capture_turns = False
 
+    #: keep ``world.target_types`` (uint8 ``[E, A]``): the entity type every agent found on its target cell in the last turn (255: invalid
+    #: action / outside the grid) -- what an agent that counts its encounters reads (``examples/iowa``).  Plain movers only.
+    record_targets = False
+
+    @property
+    def target_types(self):
+        self._ensure_engine()
+        return getattr(self.world, "target_types", None)
+
+    def _keep_turn_state(self, eng) -> None:
+        """The device's turn state at the turn in flight: ``sgw_act`` has no turn argument and keys what it draws -- exploration, drawn
+        values -- by that state (``sgw_turn_set``)."""
+        if not self._turn_capture and self._turn_state_at.get(eng.uid) != (self.epoch, self.turn):
+            eng.turn_set(self.epoch, self.turn - 1)
+            self._turn_state_at[eng.uid] = (self.epoch, self.turn)
+
     #: Tag / Cleanup agents: let the engine write what ``pov`` appends behind the window (False = ``torch.cat`` on the host: A/B and tests)
     row_tails_in_kernel = True
 
@@ -419,7 +459,8 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
                 return
             self._captured = None            # the engine was rebuilt (new entity types, another obs dtype): back to the eager loop
         if self._mixed:
-            return self._take_turn_mixed(eng, actions)
+            self._take_turn_mixed(eng, actions)
+            return self._end_of_turn(eng)
         self.turn += 1
         eng.epoch, eng.turn = self.epoch, self.turn
         self._fresh_obs = None
@@ -442,6 +483,12 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
             self._fresh_obs = (0, self.world.mutations, slot)
             for agent in self.agents:
                 agent.transition(self.world)
+        self._end_of_turn(eng)
+
+    def _end_of_turn(self, eng) -> None:
+        """Hook: device-side bookkeeping a subclass does once per turn from the step's outputs (``rewards``, ``target_types``), after the last
+        agent has acted.  It is part of a recorded turn (``capture_turn``), so it must be stream-ordered tensor work at fixed addresses: no
+        host synchronisation, no Python state that changes from turn to turn."""
 
     def turn_plan(self) -> dict:
         """Which of the loops above will play the next ``take_turn()`` (without actions), and why the faster ones do not apply: a diagnostic --
@@ -722,6 +769,8 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
                 self._turn_state_at[eng.uid] = (self.epoch, self.turn)
             if not (self._turn_capture and torch.cuda.is_current_stream_capturing()):
                 self._push_epsilon(eng, (a,))                         # (a recorded turn gets its epsilons before each replay)
+        if eng.spec.has_drawn_values:            # a drawn value is keyed by the turn in flight, like the exploration draws
+            self._keep_turn_state(eng)
         if self._mixed:                          # windows are rendered per agent at its pov: nothing to keep current
             direct = values or (action.device == eng.device and action.dtype in eng._ACTION_KINDS and action.dim() == 1
                                 and action.shape[0] == eng.num_envs and action.is_contiguous())

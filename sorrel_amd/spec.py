@@ -98,6 +98,14 @@ class WorldSpec:
     zap_beam_type: int = 0
     beam_block_mask: int = 0
     reward_total_factor: int = 1
+    # drawn values (entities.rules.DrawnValue): type t is worth type_value_alt[t] with probability value_alt_prob[t] (redrawn every
+    # turn, per cell), else type_value[t]; empty / all zero = nobody draws
+    type_value_alt: List[float] = field(default_factory=list)
+    value_alt_prob: List[float] = field(default_factory=list)
+
+    @property
+    def has_drawn_values(self) -> bool:
+        return any(float(p) > 0.0 for p in self.value_alt_prob)
 
     @property
     def num_types(self) -> int:
@@ -159,6 +167,8 @@ class WorldSpec:
         app = np.asarray(self.appearance, dtype=np.float64)
         for t in range(T):
             c.type_value[t] = float(self.type_value[t])
+            c.type_value_alt[t] = float(self.type_value_alt[t]) if t < len(self.type_value_alt) else 0.0
+            c.value_alt_prob[t] = float(self.value_alt_prob[t]) if t < len(self.value_alt_prob) else 0.0
             c.type_passable[t] = 1 if self.type_passable[t] else 0
             c.type_rule[t] = int(self.type_rule[t])
             c.spawn_prob[t] = float(self.spawn_prob[t])

@@ -167,6 +167,8 @@ class _FastPolicyTurn:
         else:
             eng.step(sweep=True, agent_begin=0, agent_end=0, write_obs=False, turn=env.turn)  # the sweep alone
             eng.observe_rows(self.rows)                                                     # every agent's window into its replay row
+        if eng.spec.has_drawn_values:                 # sgw_act keys a drawn value by the device's turn state
+            env._keep_turn_state(eng)
         h, stream = eng._h, eng._stream()
         grid, pos, acts, rew, tot = eng.grid.data_ptr(), eng.agent_pos.data_ptr(), eng.actions.data_ptr(), eng.rewards.data_ptr(), eng.total_reward.data_ptr()
         dev = eng.device

@@ -31,6 +31,7 @@ class RecordedTurns:
             self._turn_capture = False
             self._turn_windows = None
         eng.turn_end(commit_windows=self._capture_rows is None)
+        self._end_of_turn(eng)
 
     #: a recorded turn writes every window twice (a fixed address for the policy + the replay row); above this many bytes of windows per
     #: turn that costs more than the host time a replay saves while there are few agents (measured: 32x32 / 8 agents, 65 536 envs = 617 MB:

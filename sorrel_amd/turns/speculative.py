@@ -126,6 +126,8 @@ class SpeculativeTurns:
             t["agent_state"] = eng.agent_state.clone()
         if eng.agent_dir is not None:
             t["agent_dir"] = eng.agent_dir.clone()
+        if eng.target_types is not None:
+            t["target_types"] = torch.full_like(eng.target_types, 255)
         played = GridEngine(eng.spec, eng.num_envs, device=eng.device, first_env_id=eng.first_env_id, tensors=t, obs_dtype=eng.obs_dtype)
         self.__dict__["_spec_scratch"] = (eng, played)
         self._aux_engines[("speculation scratch", eng.uid)] = played      # (raise_on_status polls it; closed with the others)
@@ -199,6 +201,8 @@ class SpeculativeTurns:
         for _name, real, scratch in state:                               # the last pass played the sequential turn: its state is the turn's
             real.copy_(scratch)
         eng.rewards.copy_(played.rewards)
+        if eng.target_types is not None and played.target_types is not None:
+            eng.target_types.copy_(played.target_types)
         if eng.state_at_pov is not None:
             eng.state_at_pov.copy_(played.state_at_pov)
         self.speculation_passes = k
