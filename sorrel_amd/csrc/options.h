@@ -1,4 +1,4 @@
-// options.h -- host side of sgw.hip (included inside its anonymous namespace).
+// options.h -- host side of sgw.hip (included inside its anonymous namespace, before jit.h and plan.h, which read it).
 // Every knob of the dispatcher in ONE table, set through sgw_set_option (include/sgw.h).  The shipped library reads no
 // environment variable for any of them (rounds 1-3 grew ~30 getenv hooks; tests and tools now say what they want).
 // A NULL engine addresses the process-wide defaults that sgw_plan / sgw_create copy; an engine's own copy is frozen at
