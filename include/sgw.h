@@ -567,6 +567,38 @@ int sgw_choose_actions(sgw_engine* eng, const float* values, const int64_t* idx,
  * Stream-ordered and kept in the device's turn state, so a recorded turn follows a decaying epsilon without being recorded again. */
 int sgw_turn_epsilon(sgw_engine* eng, int32_t agent, double epsilon, void* stream);
 
+/* ---- sprite frames (sorrel/utils/visualization.py:27-176: render_sprite + image_from_array, for a batch, on the device) ----
+ * Every cell byte of `grid` names a tile of an RGBA atlas (type_tile); a frame is rows x cols tiles.  Composited frames paste the
+ * layers bottom-up the way PIL's Image.paste(layer, (0, 0), mask=layer) does on RGBA images, for each of the four bytes:
+ *     t = dst * (255 - a) + src * a + 128;   out = ((t >> 8) + t) >> 8        (a = the source pixel's alpha; layer 0 is taken as it is)
+ * Needs no engine and knows no type cap: any byte value may be a type.  All pointers are device pointers. */
+#define SGW_RENDER_COMPOSITE 0   /* out u8 [n]([k])[rows * th][cols * tw][4] */
+#define SGW_RENDER_LAYERS 1      /* out u8 [n]([k])[L][rows * th][cols * tw][4]: what render_sprite returns, one plane per layer */
+#define SGW_TILE_OPAQUE 1        /* tile_flags: every pixel of the tile has alpha 255 (what lies under it is not read) */
+#define SGW_TILE_CLEAR 2         /* tile_flags: every pixel of the tile has alpha 0 (pasting it changes nothing) */
+#define SGW_TILE_KEEP 0xFFFF     /* agent_tile: the agent shows the tile of the cell byte it stands on */
+typedef struct sgw_render_desc {
+    const uint8_t* grid;         /* [E][L][H][W] cell bytes; env e starts at grid + e * grid_env_stride */
+    const uint8_t* atlas;        /* [n_tiles][th][tw][4] RGBA, 4-byte aligned (16-byte aligned for the 16-bytes-per-lane path) */
+    const uint8_t* tile_flags;   /* [n_tiles] SGW_TILE_* computed by the caller from the atlas, or NULL (no shortcuts) */
+    const uint16_t* type_tile;   /* [256] atlas tile of every cell byte (an entry >= n_tiles shows oob_tile) */
+    const uint8_t* agent_pos;    /* [E][A][2] (y, x), or NULL: no agents */
+    const uint16_t* agent_tile;  /* [E][A]: replaces the tile of the agent's cell in agent_layer; SGW_TILE_KEEP (or any value >= n_tiles) = keep */
+    const int64_t* env_ids;      /* [n] envs to render, any order, repeats allowed; NULL = envs 0 .. E-1 (n is then E).  A frame whose
+                                    id is outside [0, E) is left unwritten */
+    const int16_t* centres;      /* [n][k][2] (y, x) or NULL: with it a frame is the (2 * vision + 1)^2 tiles around the centre, tiles
+                                    outside the map show oob_tile; without it a frame is the whole map and k counts as 1 */
+    uint8_t* out;                /* 4-byte aligned (16 for the 16-bytes-per-lane path) */
+    int64_t num_envs, n, grid_env_stride;   /* grid_env_stride 0 = L * H * W */
+    int32_t layers, height, width;          /* 1..8, 1..4096 each (1..256 with agents); one tile row holds at most 1024 columns
+                                               and layers * columns <= 4096 */
+    int32_t num_agents, agent_layer;
+    int32_t n_tiles, th, tw;                /* 1..65535 tiles of th x tw pixels, 1..64 each */
+    int32_t k, vision, oob_tile, mode;      /* mode: SGW_RENDER_COMPOSITE / SGW_RENDER_LAYERS */
+} sgw_render_desc;
+/* Asynchronous on `stream`.  Bad shapes: SGW_EINVAL with the reason in sgw_last_error(). */
+int sgw_render(const sgw_render_desc* desc, void* stream);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

@@ -23,6 +23,8 @@ STREAM_VALUE = 8            # which of its two values a type with a drawn value 
 NO_TARGET = 255             # target_types: the agent's action was invalid or aimed outside the grid
 TAIL_NONE, TAIL_AGENT_IS_IT, TAIL_POSITION_TABLE = 0, 1, 2
 OK, EINVAL, EHIP, ENOMEM = 0, -1, -2, -3
+RENDER_COMPOSITE, RENDER_LAYERS = 0, 1
+TILE_OPAQUE, TILE_CLEAR, TILE_KEEP = 1, 2, 0xFFFF
 
 
 class SgwConfig(C.Structure):
@@ -103,6 +105,21 @@ class SgwTurnRows(C.Structure):
     ]
 
 
+class SgwRenderDesc(C.Structure):
+    """Mirror of ``struct sgw_render_desc`` (include/sgw.h): one ``sgw_render`` call."""
+
+    _fields_ = [
+        ("grid", C.c_void_p), ("atlas", C.c_void_p), ("tile_flags", C.c_void_p), ("type_tile", C.c_void_p),
+        ("agent_pos", C.c_void_p), ("agent_tile", C.c_void_p), ("env_ids", C.c_void_p), ("centres", C.c_void_p),
+        ("out", C.c_void_p),
+        ("num_envs", C.c_int64), ("n", C.c_int64), ("grid_env_stride", C.c_int64),
+        ("layers", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+        ("num_agents", C.c_int32), ("agent_layer", C.c_int32),
+        ("n_tiles", C.c_int32), ("th", C.c_int32), ("tw", C.c_int32),
+        ("k", C.c_int32), ("vision", C.c_int32), ("oob_tile", C.c_int32), ("mode", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -113,7 +130,7 @@ EXPORTS = (
     "sgw_algorithmic_bytes_per_env_step", "sgw_set_timing", "sgw_get_step_time_ms", "sgw_get_step_times_ms",
     "sgw_set_auto_reset", "sgw_set_wg_per_cu", "sgw_launch_info", "sgw_capabilities", "sgw_observe_rows", "sgw_act", "sgw_observe_full",
     "sgw_set_option", "sgw_plan", "sgw_jit_stats", "sgw_jit_compile", "sgw_bind_row_tail",
-    "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions",
+    "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render",
     "sgw_last_error", "sgw_version",
 )
 
@@ -249,6 +266,8 @@ def load():
     lib.sgw_turn_prev_rows.restype = C.c_int
     lib.sgw_turn_epsilon.argtypes = [vp, C.c_int32, C.c_double, vp]
     lib.sgw_turn_epsilon.restype = C.c_int
+    lib.sgw_render.argtypes = [C.POINTER(SgwRenderDesc), vp]
+    lib.sgw_render.restype = C.c_int
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

@@ -77,6 +77,16 @@ class Agent(Entity):
     #: engine sort out whose window an earlier agent's move changed (``Environment.speculate_turns``).  Off unless a class says so.
     speculative_ok = False
 
+    #: action indices after which the agent shows ``sprite_directions[action]`` (the reference sets ``agent.sprite`` inside
+    #: ``movement(action)``): None = every action, () = never.  Read by ``sorrel_amd.utils.visualization``; the step kernels do not know it.
+    sprite_switch_actions = ()
+
+    def sprite_table(self) -> dict:
+        """kind -> list of sprites indexed by action, for every kind (state) this agent can have; one kind unless the sprite list
+        depends on the agent's state (Tag).  An entry is a sprite file path, a uint8 ``(th, tw, 4)`` array, or None (the flat tile of
+        the kind)."""
+        return {self.kind: list(getattr(self, "sprite_directions", ()))}
+
     def row_tail(self, world):
         """What ``pov`` appends behind the flattened window, as the engine can write it itself (``sgw_bind_row_tail``):
         ``(N.TAIL_AGENT_IS_IT, None)``, ``(N.TAIL_POSITION_TABLE, float32 table [H, W, n])``, or None (``pov`` appends nothing, or
@@ -120,9 +130,12 @@ class MovingAgent(Agent):
     """Agent that moves up / down / left / right (``agent.py:176-225``)."""
 
     direction = 2
-    #: sprites of the four headings in the reference (PNG paths under ``sorrel/agents/assets``); sprite rendering is outside
-    #: this engine, the attribute exists so that subclasses that index it keep importing
+    #: what the agent shows after ``movement(action)``, indexed by the ACTION number as in the reference (``agent.py:179-198``: up, down,
+    #: left, right).  An entry is a sprite file path, a uint8 ``(th, tw, 4)`` array, or None = the flat tile of the agent's kind (this
+    #: package ships no image files).  An action index beyond the list keeps the current sprite (the reference raises IndexError).
     sprite_directions = [None, None, None, None]
+    #: ``MovingAgent.act`` calls ``movement`` for every action; a subclass whose ``act`` does not says which actions do
+    sprite_switch_actions = None
 
     def movement(self, action):
         """New location for an action: an int gives the env-0 tuple (reference call shape),

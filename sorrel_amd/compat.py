@@ -19,7 +19,7 @@ or, without touching the script at all::
 ``install`` registers a meta-path finder that answers every ``sorrel`` / ``sorrel.*`` import with the ``sorrel_amd``
 module of the same relative name (the SAME module object: ``sorrel.environment.Environment is
 sorrel_amd.environment.Environment``).  Parts of the reference outside the hot path this package rebuilds (models beyond
-``BaseModel`` / ``RandomModel``, logging, visualisation, the CLI, NodeWorld, chess) do not exist here; importing
+``BaseModel`` / ``RandomModel``, logging, the CLI, NodeWorld, chess) do not exist here; importing
 them fails with a ``ModuleNotFoundError`` that says so.  If a real ``sorrel`` distribution is importable, ``install``
 refuses to shadow it unless ``force=True``.
 """
@@ -37,14 +37,13 @@ _TARGET = "sorrel_amd"
 MIRRORED = (
     "", "environment", "worlds", "worlds.gridworld", "entities", "entities.entity", "entities.basic_entities", "agents",
     "agents.agent", "observation", "observation.observation_spec", "observation.visual_field", "observation.embedding",
-    "action", "action.action_spec", "utils", "utils.helpers", "location", "buffers", "models", "models.base_model",
+    "action", "action.action_spec", "utils", "utils.helpers", "utils.visualization", "location", "buffers", "models", "models.base_model",
     "examples", "examples.treasurehunt", "examples.tag", "examples.cleanup", "examples.iowa",
 )
 
 #: reference modules that are deliberately NOT rebuilt (out of scope) -> a clear error, not a stub
 OUT_OF_SCOPE = {
     "utils.logging": "per-epoch scalar logging (pass any object with record_turn(epoch, loss, reward, epsilon) as `logger`)",
-    "utils.visualization": "sprite rendering / GIFs",
     "cli": "the `sorrel run` launcher",
     "threadsafe": "RLock wrappers around a shared model",
     "worlds.nodeworld": "the graph world for LLM agents",

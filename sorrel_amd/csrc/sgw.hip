@@ -29,6 +29,7 @@
 //                                        env's loads issued ahead of this env's observation stores
 //   phase_kernel<ONEHOT>                 one policy-driven phase of a world above 4 KiB without staging the env
 //   reset_kernel, random_actions_kernel, init_agent_state_kernel, reduce_stage1/2
+//   render_kernel<TW, VEC, LDS_ATLAS>    sprite frames of the world tensor (render.h): engine-free, write-bound
 // then the host side: options.h, jit.h (the in-process specialiser), plan.h (validation, table building, kernel selection: the planner), and below
 // the engine, the launchers and the C entry points.
 //
@@ -67,6 +68,7 @@ namespace {
 #include "phase.h"
 #include "small_kernels.h"
 #include "resolve.h"
+#include "render.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -1155,6 +1157,85 @@ int sgw_gather_rows(const float* src, int64_t row_elems, const int64_t* idx, int
     const bool v2 = (row_elems & 1) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 7) == 0;
     if (v2) hipLaunchKernelGGL(gather_rows_kernel<2>, dim3(blocks), dim3(kBlock), 0, s, src, row_elems, idx, n, dst);
     else hipLaunchKernelGGL(gather_rows_kernel<1>, dim3(blocks), dim3(kBlock), 0, s, src, row_elems, idx, n, dst);
+    HIP_TRY(hipGetLastError());
+    return SGW_OK;
+}
+
+// ---------------------------------------------------------------- sprite frames (render.h)
+int sgw_render(const sgw_render_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_render: desc is NULL");
+    if (!d->grid || !d->atlas || !d->type_tile || !d->out) return fail(SGW_EINVAL, "sgw_render: grid, atlas, type_tile and out must not be NULL");
+    if (d->num_envs < 1) return fail(SGW_EINVAL, "sgw_render: num_envs = %lld", (long long)d->num_envs);
+    if (d->layers < 1 || d->layers > 8) return fail(SGW_EINVAL, "sgw_render: layers = %d outside 1..8", d->layers);
+    if (d->height < 1 || d->height > 4096 || d->width < 1 || d->width > 4096)
+        return fail(SGW_EINVAL, "sgw_render: map %d x %d outside 1..4096", d->height, d->width);
+    if (d->th < 1 || d->th > 64 || d->tw < 1 || d->tw > 64) return fail(SGW_EINVAL, "sgw_render: tile %d x %d outside 1..64", d->th, d->tw);
+    if (d->n_tiles < 1 || d->n_tiles > 65535) return fail(SGW_EINVAL, "sgw_render: n_tiles = %d outside 1..65535", d->n_tiles);
+    if (d->oob_tile < 0 || d->oob_tile >= d->n_tiles) return fail(SGW_EINVAL, "sgw_render: oob_tile = %d is not a tile of the atlas", d->oob_tile);
+    if (d->mode != SGW_RENDER_COMPOSITE && d->mode != SGW_RENDER_LAYERS) return fail(SGW_EINVAL, "sgw_render: unknown mode %d", d->mode);
+    const int64_t cells = (int64_t)d->layers * d->height * d->width;
+    const int64_t env_stride = d->grid_env_stride ? d->grid_env_stride : cells;
+    if (env_stride < cells) return fail(SGW_EINVAL, "sgw_render: grid_env_stride is smaller than one env");
+    if (d->agent_pos) {
+        if (!d->agent_tile) return fail(SGW_EINVAL, "sgw_render: agent_pos without agent_tile");
+        if (d->num_agents < 1) return fail(SGW_EINVAL, "sgw_render: num_agents = %d", d->num_agents);
+        if (d->agent_layer < 0 || d->agent_layer >= d->layers) return fail(SGW_EINVAL, "sgw_render: agent_layer = %d outside the world's layers", d->agent_layer);
+        if (d->height > 256 || d->width > 256) return fail(SGW_EINVAL, "sgw_render: agent positions are bytes: the map must be at most 256 x 256");
+        if (reinterpret_cast<uintptr_t>(d->agent_tile) & 1) return fail(SGW_EINVAL, "sgw_render: agent_tile is not 2-byte aligned");
+    }
+    int64_t n = d->env_ids ? d->n : d->num_envs;
+    if (n < 0) return fail(SGW_EINVAL, "sgw_render: n = %lld", (long long)n);
+    int k = 1, rows = d->height, cols = d->width;
+    if (d->centres) {
+        if (d->k < 1) return fail(SGW_EINVAL, "sgw_render: k = %d windows per env", d->k);
+        if (d->vision < 0 || d->vision > 511) return fail(SGW_EINVAL, "sgw_render: vision = %d outside 0..511", d->vision);
+        k = d->k;
+        rows = cols = 2 * d->vision + 1;
+    }
+    if (cols > kRenderMaxCols || (int64_t)d->layers * cols > kRenderMaxCells)
+        return fail(SGW_EINVAL, "sgw_render: %d layers x %d columns: a tile row holds at most %d columns and layers * columns <= %d", d->layers, cols, kRenderMaxCols, kRenderMaxCells);
+    const uintptr_t a_out = reinterpret_cast<uintptr_t>(d->out), a_atlas = reinterpret_cast<uintptr_t>(d->atlas);
+    if ((a_out & 3) || (a_atlas & 3)) return fail(SGW_EINVAL, "sgw_render: out and atlas must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d->type_tile) & 1) || (reinterpret_cast<uintptr_t>(d->centres) & 1) || (reinterpret_cast<uintptr_t>(d->env_ids) & 7))
+        return fail(SGW_EINVAL, "sgw_render: misaligned type_tile / centres / env_ids");
+    if (n == 0) return SGW_OK;
+    RenderParams p{};
+    p.grid = d->grid; p.atlas = d->atlas; p.tile_flags = d->tile_flags; p.type_tile = d->type_tile;
+    p.agent_pos = d->agent_pos; p.agent_tile = d->agent_tile; p.env_ids = d->env_ids; p.centres = d->centres; p.out = d->out;
+    p.E = d->num_envs; p.n = n; p.env_stride = env_stride;
+    p.L = d->layers; p.H = d->height; p.W = d->width; p.A = d->agent_pos ? d->num_agents : 0; p.agent_layer = d->agent_layer;
+    p.n_tiles = d->n_tiles; p.th = d->th; p.tw = d->tw; p.k = k; p.vision = d->vision; p.oob_tile = d->oob_tile;
+    p.per_layer = d->mode == SGW_RENDER_LAYERS;
+    p.rows = rows; p.cols = cols;
+    p.span_bytes = (int64_t)d->th * cols * d->tw * 4;
+    p.tile_bytes = d->th * d->tw * 4;
+    p.tile_pitch = p.tile_bytes + kRenderAtlasPad;
+    const bool vec4 = (d->tw % 4) == 0 && !(a_out & 15) && !(a_atlas & 15);
+    p.units_per_row = cols * d->tw / (vec4 ? 4 : 1);
+    const bool lds_atlas = (int64_t)d->n_tiles * p.tile_pitch <= kRenderAtlasLds;
+    const size_t lds = lds_atlas ? (size_t)d->n_tiles * p.tile_pitch : 0;
+    static int cus[64] = {};
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || cus[dev] == 0) {
+        int c = 0;
+        HIP_TRY(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
+        if (c < 1) c = 256;
+        if (dev >= 0 && dev < 64) cus[dev] = c;
+        else cus[0] = cus[0] ? cus[0] : c, dev = 0;
+    }
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(160 * 1024) / (kRenderStaticLds + lds)));
+    const int64_t resident = (int64_t)cus[dev] * per_cu;
+    // tile rows per work item: as many as the cell table holds, halved while the launch has fewer than two items per resident workgroup
+    int rpi = std::max(1, std::min(rows, kRenderMaxCells / (d->layers * cols)));
+    while (rpi > 1 && n * k * ceil_div(rows, rpi) < 2 * resident) rpi = (rpi + 1) / 2;
+    p.rpi = rpi;
+    p.items_per_frame = (int)ceil_div(rows, rpi);
+    p.items = n * k * p.items_per_frame;
+    const unsigned blocks = (unsigned)std::min<int64_t>(p.items, resident);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vec4) { if (lds_atlas) launch_render<4, true>(p, blocks, lds, s); else launch_render<4, false>(p, blocks, lds, s); }
+    else { if (lds_atlas) launch_render<1, true>(p, blocks, lds, s); else launch_render<1, false>(p, blocks, lds, s); }
     HIP_TRY(hipGetLastError());
     return SGW_OK;
 }

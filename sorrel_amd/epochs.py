@@ -12,6 +12,52 @@ import torch
 from sorrel_amd.agents.agent import Agent
 
 
+class _Film:
+    """The frames of one animated epoch: rendered on the device into a ring ``[T, n, h, w, 4]`` before every turn, copied to the host
+    once, written as one GIF."""
+
+    def __init__(self, env, max_turns: int):
+        from sorrel_amd.utils.visualization import renderer_of
+
+        exp = env.config.experiment
+        which = exp.get("animate_env", 0) if hasattr(exp, "get") else getattr(exp, "animate_env", 0)
+        self.env = env
+        self.sheet = not isinstance(which, int)
+        w = env.world
+        self.env_ids = torch.as_tensor([which] if isinstance(which, int) else list(which), dtype=torch.int64, device=w.device)
+        self.renderer = renderer_of(w)
+        th, tw = self.renderer.tile_size
+        self.ring = torch.empty((max(1, int(max_turns)), len(self.env_ids), w.height * th, w.width * tw, 4), dtype=torch.uint8, device=w.device)
+        self.count = 0
+
+    def shoot(self) -> None:
+        if self.count < self.ring.shape[0]:
+            self.renderer.frames(self.env_ids, out=self.ring[self.count])
+            self.count += 1
+
+    def play(self, max_turns: int) -> None:
+        """The reference's loop (``environment.py:160-168``) with the recorded graph, if there is one, set aside for the epoch."""
+        env = self.env
+        captured, env._captured = env._captured, None
+        try:
+            while env.turn < max_turns:
+                self.shoot()
+                env.take_turn()
+                if env.world.is_done and env.stop_if_done:
+                    break
+        finally:
+            env._captured = captured
+
+    def save(self, path) -> None:
+        if self.count == 0:
+            return
+        from sorrel_amd.utils.visualization import SpriteRenderer
+
+        frames = self.ring[:self.count]
+        frames = SpriteRenderer.contact_sheet(frames) if self.sheet else frames[:, 0]
+        SpriteRenderer.to_gif(path, frames.cpu())
+
+
 class EpochLoops:
     """Mixed into ``sorrel_amd.environment.Environment``."""
 
@@ -56,8 +102,13 @@ class EpochLoops:
         agent's, as in the reference: assignment, not a sum) -> ``logger.record_turn(epoch, loss, reward, epsilon)``
         -> epsilon decay -> model checkpoint every ``record_period`` epochs when ``config.model.save_weights``
         (``sorrel/environment.py:148-211``).  The reward logged is the mean of ``world.total_reward`` over ALL
-        envs of ALL ranks (the one RCCL all-reduce); the per-epoch metric dicts are returned.  ``animate`` is
-        accepted for signature compatibility; sprite rendering is outside this engine."""
+        envs of ALL ranks (the one RCCL all-reduce); the per-epoch metric dicts are returned.
+
+        ``animate`` (``sorrel/environment.py:142-175``; off by default here): on epochs with ``epoch % record_period == 0`` the frame
+        of env ``config.experiment.animate_env`` (default 0; a list: a contact sheet) is rendered on the device before every
+        ``take_turn`` into a ring, copied to the host once at the end of the epoch and written to
+        ``<output_dir>/gifs/<ClassName>_epoch<N>.gif``.  Those epochs play turn by turn (no one-call rollout, no recorded graph);
+        the turns compute the same either way, so the metrics do not depend on ``animate``."""
         from sorrel_amd import distributed as D
 
         exp = self.config.experiment
@@ -66,25 +117,30 @@ class EpochLoops:
         record_period = int(exp.record_period) if (hasattr(exp, "record_period") or "record_period" in exp) else 1
         save_weights = bool(self._cfg_model("save_weights", False))
         decay = self._cfg_model("epsilon_decay", None)
-        out_dir = self._output_dir(output_dir) if save_weights else None
+        out_dir = self._output_dir(output_dir) if (save_weights or animate) else None
         capture = bool(self.capture_turns or (exp.get("capture_turns", False) if hasattr(exp, "get") else getattr(exp, "capture_turns", False)))
         history = []
         for epoch in range(epochs + 1):
             self.reset()
             for agent in self.agents:
                 self._model_start_epoch_action(agent, epoch)
-            if all(getattr(a.model, "device_random", False) for a in self.agents) and not self.stop_if_done \
+            film = _Film(self, max_turns) if animate and epoch % record_period == 0 else None
+            if film is not None:
+                film.play(max_turns)                       # frame, take_turn, frame, take_turn, ... in the eager loop
+            elif all(getattr(a.model, "device_random", False) for a in self.agents) and not self.stop_if_done \
                     and self._stock_take_turn():
                 self.rollout(max_turns - self.turn)        # the whole epoch in one engine call (a subclass that overrides
                                                            # take_turn gets its per-turn loop below, as in the reference)
             elif capture and self._captured is None and not self.stop_if_done and self._stock_take_turn() \
                     and max_turns - self.turn > 2:
                 capture = self.capture_turn(warmup=2) is not None      # (two real turns of this epoch; not tried again when it fails)
-            while self.turn < max_turns:
+            while film is None and self.turn < max_turns:
                 self.take_turn()
                 if self.world.is_done and self.stop_if_done:
                     break
             self.world.is_done = True
+            if film is not None:
+                film.save(out_dir / "gifs" / f"{type(self).__name__}_epoch{epoch}.gif")
             self.raise_on_status()
             m = D.rollout_metrics(self._ensure_engine(), all_reduce=all_reduce)
             for agent in self.agents:
@@ -142,20 +198,24 @@ class EpochLoops:
         exp = self.config.experiment
         capture = bool(self.capture_turns or (exp.get("capture_turns", False) if hasattr(exp, "get") else getattr(exp, "capture_turns", False)))
         ring = None
+        record_period = int(exp.record_period) if (hasattr(exp, "record_period") or "record_period" in exp) else 1
         for game in range(num_games):
             self.reset()
             for agent in self.agents:
                 self._model_start_epoch_action(agent, game)
             eng = self._ensure_engine()
+            film = _Film(self, T) if animate and game % record_period == 0 else None
             if device_random:
                 if ring is None:
                     ring = TurnBuffer(T, E, eng.spec.obs_shape, device=eng.device, obs_dtype=eng.obs_dtype,
                                       positions=record_positions)
                 ring.clear()
-                if one_call:
+                if one_call and film is None:
                     self.collect(T, ring)
                 else:
                     while self.turn < T:
+                        if film is not None:
+                            film.shoot()
                         self.take_turn()
                         eng = self._ensure_engine()
                         ring.obs[ring.slot()].copy_(eng.obs)
@@ -166,6 +226,8 @@ class EpochLoops:
                 for a, sg in enumerate(saved):
                     st, ac, rw, dn = ring.agent_view(a)
                     sg.add_turns(st[:n], ac[:n], rw[:n], dn[:n], positions=None if ring.positions is None else ring.positions[:n, :, a])
+            elif film is not None:
+                film.play(T)
             else:
                 if capture and self._captured is None and not self.stop_if_done and self._stock_take_turn() and T - self.turn > 2:
                     capture = self.capture_turn(warmup=2) is not None      # (capture_turns: as in run_experiment)
@@ -174,6 +236,8 @@ class EpochLoops:
                     if self.world.is_done and self.stop_if_done:
                         break
             self.world.is_done = True
+            if film is not None:
+                film.save(out_dir / "gifs" / f"{type(self).__name__}_epoch{game}.gif")
             self.raise_on_status()
             for agent, sg in zip(self.agents, saved):
                 self._model_end_epoch_action(agent, game)

@@ -51,6 +51,8 @@ class CleanupAgent(MovingAgent):
 
     speculative_ok = True        # pov = the engine's row (window + positional code, row_tail), get_action = model.take_action: the fast eager loop applies
 
+    sprite_switch_actions = (0, 1, 2, 3)   # movement() runs for the four moves only (agents.py:152-154), indexed by the action number
+
     def __init__(self, observation_spec, action_spec, model, beam_radius: int = 3):
         super().__init__(observation_spec, action_spec, model)
         self.interaction_rule = CleanupRule(beam_radius, CleanBeam, ZapBeam)

@@ -19,6 +19,14 @@ class TagAgent(MovingAgent):
         self.reward_per_turn = reward_per_turn
         self.interaction_rule = TagRule(reward_per_turn)
         self.kind = "NotIt"          # default appearance (agents.py:23)
+        # the two sprite lists of agents.py:25-36, indexed by action; None = the flat tile of the kind
+        self._not_it_sprite_dirs = [None, None, None, None]
+        self._it_sprite_dirs = [None, None, None, None]
+
+    def sprite_table(self) -> dict:
+        """The list in force is the one of the state the agent had when it moved: the ``it`` setter swaps the list, not the sprite
+        (agents.py:44-51), so a tagged agent keeps its colour until its next move."""
+        return {"It": list(self._it_sprite_dirs), "NotIt": list(self._not_it_sprite_dirs)}
 
     def as_kind(self, kind: str) -> "TagAgent":
         """Prototype of this agent with another appearance (the engine registers both types)."""

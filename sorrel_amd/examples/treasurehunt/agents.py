@@ -7,6 +7,8 @@ from sorrel_amd.agents import MovingAgent
 class TreasurehuntAgent(MovingAgent):
     speculative_ok = True        # pov = the flattened window, get_action = model.take_action (frame stacks excepted: checked per turn)
 
+    sprite_switch_actions = ()   # the reference's act computes the move itself and never calls movement(): the sprite never changes
+
     def __init__(self, observation_spec, action_spec, model):
         super().__init__(observation_spec, action_spec, model)
 
