@@ -231,6 +231,18 @@ __device__ __forceinline__ uint32_t word_of(const U4& v, int i) {
     return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
 }
 
+// `v` with lane `lane` replaced by `val`, both wave-uniform: ONE vector instruction where `l == lane ? val : v` costs a move and a select.
+// The lane select goes through M0: a gfx9 vector instruction reads one scalar register only (`val` here).  readfirstlane: nothing where
+// the compiler holds the operand in a scalar register already; where it chose a vector register for a uniform value, the "s" constraint
+// alone would not move it.
+__device__ __forceinline__ uint32_t write_lane(uint32_t v, const uint32_t val, const int lane) {
+    asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0"
+        : "+v"(v)
+        : "s"(__builtin_amdgcn_readfirstlane((int)val)), "s"(__builtin_amdgcn_readfirstlane(lane))
+        : "m0");
+    return v;
+}
+
 // Drawn values: the u32 that decides what the entity on `cell` (layer-major cell index, the spawn stream's index) is worth in `turn`.
 // One draw per (cell, turn) is enough: the first agent that steps on a deck removes it (sorrel/examples/iowa/agents.py:47-60).
 __device__ __forceinline__ uint32_t value_draw(const Params& p, const uint32_t cell, const uint32_t turn, const uint32_t env_id, const uint32_t ep4) {

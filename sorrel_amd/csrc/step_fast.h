@@ -207,6 +207,12 @@ __device__ __forceinline__ void fast_rows_emit(const Params& p, const RowPtrs* r
     }
 }
 
+// The hit bits of all of a lane's units as ONE mask (16 per unit): 32 bits for up to two units per lane, 64 beyond.
+template <bool WIDE> struct HitMask { typedef uint32_t type; };
+template <> struct HitMask<true> { typedef uint64_t type; };
+__device__ __forceinline__ uint32_t hm_first(const uint32_t m) { return (uint32_t)__ffs(m) - 1u; }
+__device__ __forceinline__ uint32_t hm_first(const uint64_t m) { return (uint32_t)__ffsll((unsigned long long)m) - 1u; }
+
 // ROWS (round 5): the instance behind sgw_sweep_observe_rows -- the sweep and EVERY agent's window in one launch, each window going to
 // its agent's own destination (rp->p[a] + env * rp->stride: the row of that agent's replay buffer) instead of the [E][A][C][V][V] tensor.
 // Only the emit differs (see there); compiled for compile-time shapes with the whole-env burst.
@@ -420,6 +426,8 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
         const uint32_t nturns = MULTI ? p.nturns : 1u;
         for (uint32_t tix = 0; tix < nturns; ++tix) {
         const uint32_t turn = turn0 + tix;
+        constexpr uint32_t kNotDrawn = 0xFFFFFFFFu;
+        if (rnd) act = kNotDrawn;   // (the spawn kinds' Philox pass below may draw this turn's actions as well: a lane's own mark instead of a flag in scalar registers)
         if constexpr (RULES) {
             gsync<1>();
             if (do_sweep) {
@@ -454,29 +462,63 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                 // the rare second draws of ALL the lane's units in ONE loop: the wave pays a Philox block per iteration whatever the number
                 // of lanes that still hold a hit, so a loop per unit cost ~1.2 blocks per spawning LAYER (two or three in own-entity
                 // worlds); merged, the iterations are the largest hit count of any lane over all its units (~1.5 blocks)
-                auto kind_draw = [&](const uint32_t b) {
-                    const uint32_t off = ((uint32_t)lane + 64u * (b >> 4)) * 16u + (b & 15u);   // byte offset == RNG index
-                    const U4 kw = philox4x32_10<kOwnKeys>(opaque(off >> 2), turn, env_id, ep4 | SGW_STREAM_SPAWN_KIND, p.seed_lo, p.seed_hi);
-                    const uint32_t pick = __umulhi(word_of(kw, off & 3u), p.spawn_n);
-                    lg[off] = (uint8_t)(((pick < 4 ? p.choice_lo : p.choice_hi) >> (8 * (pick & 3u))) & 0xFFu);
-                };
-                if constexpr (NU <= 2) {
-                    uint32_t hm = hits[0];
-                    if constexpr (NU == 2) hm |= hits[1] << 16;
-                    while (hm) {
-                        const uint32_t b = (uint32_t)__ffs(hm) - 1u;
-                        hm &= hm - 1u;
-                        kind_draw(b);
+                typedef typename HitMask<(NU > 2)>::type hm_t;
+                static_assert(NU <= 4, "16 hit bits per unit, four units per lane");
+                hm_t hm = 0;
+#pragma unroll
+                for (int k = 0; k < NU; ++k) hm |= (hm_t)hits[k] << (16 * k);
+                auto unit_off = [&](const uint32_t b) { return ((uint32_t)lane + 64u * (b >> 4)) * 16u + (b & 15u); };   // byte offset == RNG index
+                auto kind_of = [&](const uint32_t pick) { return (uint8_t)(((pick < 4 ? p.choice_lo : p.choice_hi) >> (8 * (pick & 3u))) & 0xFFu); };
+                // One Philox pass for the turn's rare draws (a launch that stages whole envs and draws its actions): the wave's spawn hits are
+                // compacted into a list of byte offsets -- level j of the loop takes the j-th hit of every lane that has one, its slot is the
+                // count of such lanes below it -- in the first bytes of the observation staging area, which nothing has written yet in this
+                // turn (a rollout's previous burst lies behind the gsync above).  If the list and the agents fit the wave together, lane a < A
+                // draws agent a's action and lane A + i the kind of hit i in the SAME block: index and stream are per-lane values.  (Apart: a
+                // block for the 8 action lanes of config 3 and ~1.6 blocks for its ~4.5 hits per turn.)
+                uint32_t nlist = 0;
+                bool fused = false;
+                if constexpr (!ROWS && !MULTI) {   // (the turn-loop instances are short of registers as they are: they keep the two passes)
+                    uint32_t fl = p.flags;   // (its own copy of the kernel argument: sharing `stage && write_obs` with the burst far below keeps that mask alive
+                    asm("" : "+s"(fl));      // across the whole agent loop, in a kernel that is out of scalar registers)
+                    if (stage && !(fl & SGW_STEP_NO_OBS) && p.do_move && rnd && p.a0 == 0 && p.a1 == p.A && p.obs_stage >= 256) {   // (every agent acts: lanes 0 .. A-1)
+                        uint16_t* list = reinterpret_cast<uint16_t*>(ob);
+                        const uint32_t room = 64u - (uint32_t)p.A;
+                        hm_t rest = hm;
+                        uint64_t m = __ballot(rest != 0);
+                        while (m != 0 && nlist <= room) {   // (a list that does not fit -- spawn_full, a large spawn_prob, many agents -- ends with nlist > room)
+                            if (rest != 0) {
+                                const uint32_t slot = nlist + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                                list[slot] = (uint16_t)unit_off(hm_first(rest));   // (slot <= room + 63: inside the 256 bytes tested above)
+                                rest &= rest - 1u;
+                            }
+                            nlist += (uint32_t)__popcll(m);
+                            m = __ballot(rest != 0);
+                        }
+                        fused = m == 0 && nlist <= room;
+                    }
+                }
+                if (fused) {
+                    gsync<1>();
+                    const uint32_t na = (uint32_t)p.A;
+                    if ((uint32_t)lane < na + nlist) {
+                        const bool hit = (uint32_t)lane >= na;
+                        const uint32_t off = reinterpret_cast<const uint16_t*>(ob)[((uint32_t)lane - na) & 63u];   // (an action lane reads a slot it does not use)
+                        const uint32_t ix = hit ? off : (uint32_t)lane;
+                        const U4 w = philox4x32_10<kOwnKeys>(opaque(ix >> 2), turn, env_id, ep4 | (hit ? SGW_STREAM_SPAWN_KIND : SGW_STREAM_ACTION), p.seed_lo, p.seed_hi);
+                        const uint32_t d = __umulhi(word_of(w, ix & 3u), hit ? p.spawn_n : (uint32_t)p.nact);
+                        if (hit) {
+                            lg[off] = kind_of(d);
+                        } else {
+                            act = d;
+                            p.actions[tix * p.ts_act + env * p.A + lane] = (uint8_t)d;
+                        }
                     }
                 } else {
-                    static_assert(NU <= 4, "16 hit bits per unit, four units per lane");
-                    uint64_t hm = 0;
-#pragma unroll
-                    for (int k = 0; k < NU; ++k) hm |= (uint64_t)hits[k] << (16 * k);
                     while (hm) {
-                        const uint32_t b = (uint32_t)__ffsll((unsigned long long)hm) - 1u;
-                        hm &= hm - 1ull;
-                        kind_draw(b);
+                        const uint32_t off = unit_off(hm_first(hm));
+                        hm &= hm - 1u;
+                        const U4 kw = philox4x32_10<kOwnKeys>(opaque(off >> 2), turn, env_id, ep4 | SGW_STREAM_SPAWN_KIND, p.seed_lo, p.seed_hi);
+                        lg[off] = kind_of(__umulhi(word_of(kw, off & 3u), p.spawn_n));
                     }
                 }
                 // the last, partly filled round of units (a 24x24x2 map: 72 units = one full round + 8) as DWORDS on the LDS copy: a
@@ -496,10 +538,12 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
         npos = yx;                               // position if the move succeeds
         if (p.do_move && mine) {
             if (rnd) {
-                const U4 w = philox4x32_10<kOwnKeys>(opaque((uint32_t)lane >> 2), turn, env_id, ep4 | SGW_STREAM_ACTION,
-                                           p.seed_lo, p.seed_hi);
-                act = __umulhi(word_of(w, lane & 3), (uint32_t)p.nact);
-                p.actions[tix * p.ts_act + env * p.A + lane] = (uint8_t)act;
+                if (act == kNotDrawn) {
+                    const U4 w = philox4x32_10<kOwnKeys>(opaque((uint32_t)lane >> 2), turn, env_id, ep4 | SGW_STREAM_ACTION,
+                                               p.seed_lo, p.seed_hi);
+                    act = __umulhi(word_of(w, lane & 3), (uint32_t)p.nact);
+                    p.actions[tix * p.ts_act + env * p.A + lane] = (uint8_t)act;
+                }
             } else if (tix > 0) {
                 act = p.actions[tix * p.ts_act + env * p.A + lane];
             }
@@ -532,6 +576,11 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
         }
         rew_bits = 0;
         moved = 0;
+        // Plain movers: iteration a of the loop writes lane a's records -- its reward, and (bit 0) whether it moved and (bit 1) whether it found a
+        // bad type -- with one v_writelane each, out of scalar registers (a move and a select per record and agent before, ~8 vector instructions
+        // per agent on a kernel that is bound by them); the bits are taken apart once behind the loop
+        constexpr bool kScalarBook = !TAG && !RULES;
+        [[maybe_unused]] uint32_t book = 0;
         const int64_t turn_obs = tix * p.ts_obs;   // this turn's observation slot (elements)
         if constexpr (kStageAlways) {
             ch_a0 = 0;
@@ -623,6 +672,14 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             }
             gsync<1>();
         };
+        // what a window cell outside the map counts, in VECTOR registers across the agent loop (out of scalar ones the select below costs a move
+        // per counter word, agent and cell round: a vector instruction reads the condition OR a scalar operand); the instances with registers to spare
+        [[maybe_unused]] uint32_t fill_v[NW];
+        constexpr bool kFillRegs = ONEHOT && kStatic && !RULES && !STAGE && !P3 && !I16;
+        if constexpr (kFillRegs) {
+#pragma unroll
+            for (int q = 0; q < NW; ++q) fill_v[q] = opaque(p.fill_delta[q]);
+        }
         // ---- agents, strictly in list order (SGW_STEP_OBS_NEXT: one extra, observe-only iteration for agent a1)
         const int a_end = (p.obs_next && p.a1 < p.A) ? p.a1 + 1 : p.a1;
         for (int a = p.a0; a < a_end; ++a) {
@@ -637,10 +694,10 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                     ch_a0 = a;
                 }
             }
-            const int s_o = __builtin_amdgcn_readlane((int)oaddr_v, a);
+            const uint32_t yx_a = (uint32_t)__builtin_amdgcn_readlane((int)yx, a);   // (one lane read: row, column and own cell follow in scalar registers)
+            const int y = (int)(yx_a & 0xFFu), x = (int)(yx_a >> 8);
+            const int s_o = zoff + y * W + x;
             if (p.obs_next ? a == p.a1 : write_obs) {
-                const int y = __builtin_amdgcn_readlane((int)py, a);
-                const int x = __builtin_amdgcn_readlane((int)px, a);
                 const int cbase = s_o - zoff;
                 float* obase = p.obs + turn_obs + ((env * p.obs_A + (a - p.obs_a0)) * (int64_t)C) * VV;
 #pragma unroll
@@ -672,7 +729,7 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                                 }
                             }
 #pragma unroll
-                            for (int q = 0; q < NW; ++q) cnt[q] = inb ? cnt[q] : (P3 ? p.fill_delta3 : I16 ? p.fill_delta16[q] : p.fill_delta[q]);
+                            for (int q = 0; q < NW; ++q) cnt[q] = inb ? cnt[q] : (kFillRegs ? fill_v[q] : P3 ? p.fill_delta3 : I16 ? p.fill_delta16[q] : p.fill_delta[q]);
                             // the count of channel c: a byte of the counter words, (P3) a 3-bit field of the one word, (I16) a 16-bit field clipped to 255
                             auto chan = [&](const int c) -> uint32_t {
                                 if constexpr (P3) return (cnt[0] >> (3 * c)) & 7u;
@@ -790,7 +847,7 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                         v_hi = (uint32_t)(__double_as_longlong(dv) >> 32);
                         v_f = __float_as_uint((float)dv);       // the float32 reward is the rounding of the double the total adds
                     }
-                    xv = lane == a ? (valid ? t : 255u) : xv;   // what world.observe(new_location) returned
+                    xv = write_lane(xv, valid ? t : 255u, a);   // what world.observe(new_location) returned
                 }
             }
             const bool pass = tok && ((p.pass_mask >> tl) & 1u);
@@ -798,10 +855,14 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                 lg[s_t] = (uint8_t)my_type;
                 lg[s_o] = (uint8_t)p.default_type;
             }
-            moved = lane == a ? (pass ? 1u : 0u) : moved;
+            if constexpr (kScalarBook) book = write_lane(book, tok ? (p.pass_mask >> tl) & 1u : (valid ? 2u : 0u), a);   // (selects on scalars; `pass` itself lives as a lane mask)
+            else moved = lane == a ? (pass ? 1u : 0u) : moved;
             if constexpr (!TAG) {
-                if (tok) tot += __longlong_as_double(((long long)v_hi << 32) | v_lo);   // reward BEFORE the move; float64, agent order
-                rew_bits = lane == a ? (tok ? v_f : 0u) : rew_bits;
+                // reward BEFORE the move; float64, agent order.  No reward adds -0.0, which leaves every total as it is (bit for bit, a -0.0
+                // included): the choice is made on the scalar pair, the add itself is unconditional
+                tot += __longlong_as_double(tok ? (long long)(((uint64_t)v_hi << 32) | v_lo) : (long long)0x8000000000000000ull);
+                if constexpr (kScalarBook) rew_bits = write_lane(rew_bits, tok ? v_f : 0u, a);
+                else rew_bits = lane == a ? (tok ? v_f : 0u) : rew_bits;
             } else {
                 // ---- TagAgent.act (sorrel/examples/tag/agents.py:84-106), scalar: the four neighbours of the
                 // cell the agent now stands on, in Location.adjacent order (up, right, down, left; off-map
@@ -844,8 +905,13 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                 tot += val;
                 rew_bits = lane == a ? __float_as_uint((float)val) : rew_bits;
             }
-            if (valid && !tok) st_lane |= SGW_STATUS_BAD_TYPE;
+            if constexpr (!kScalarBook)
+                if (valid && !tok) st_lane |= SGW_STATUS_BAD_TYPE;
             gsync<1>();
+        }
+        if constexpr (kScalarBook) {
+            moved = book & 1u;
+            if (book & 2u) st_lane |= SGW_STATUS_BAD_TYPE;   // (by the agent's own lane; every stepped lane reported it before)
         }
 
         STAMP(4);   // agent loop done
@@ -915,8 +981,19 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             } else {
                 uint4* dst = reinterpret_cast<uint4*>(p.grid + env * p.env_stride);
 #pragma unroll
-                for (int k = 0; k < NU; ++k)
+                for (int k = 0; k < NU; ++k) {
+                    // A full round of the register sweep is 1 KiB at a multiple of 1 KiB inside the env (whole 128-byte lines where the env stride is a
+                    // multiple of 128, as for every map whose layers fill rounds): one in which nothing spawned and which holds no cell of the agents' layer still is what was loaded,
+                    // and stays where it is (config 3: the Sand layer, half of the grid bytes).  Single-turn launches only: the hits are the
+                    // last turn's.  A round with the ragged last unit is written (its padding bytes were set above).
+                    if constexpr (kStatic && !RULES && !TAG && !MULTI) {
+                        if (k < kFullRounds && (k + 1) * 1024 <= TL * TH * TW) {
+                            const bool agents_here = zoff < (k + 1) * 1024 && zoff + HW > k * 1024;
+                            if (!agents_here && __ballot(hits[k] != 0) == 0) continue;
+                        }
+                    }
                     if (lane + 64 * k < nunits) dst[lane + 64 * k] = lg16[lane + 64 * k];
+                }
                 if constexpr (RULES || !kStatic)
                     for (int i = 64 * NU + lane; i < nunits; i += 64) dst[i] = lg16[i];
             }
