@@ -227,6 +227,66 @@ __device__ __forceinline__ uint32_t opaque(uint32_t v) {
     return v;
 }
 
+// The sweep's blocks of one wave and turn differ in their first counter word only (the dword's index): turn, env and epoch | stream are
+// wave-uniform, and with them everything of the first rounds that those words alone decide -- round 1's M1 * c2 and its n0, round 2's
+// M0 * n0 -- and every uniform pair an exclusive-or of those rounds meets (a counter word and its round key).  philox_uniform computes them
+// once per wave, in scalar registers, and keeps the four folded words as VECTOR copies: a block then starts with neither a uniform
+// move (xor3 takes two vector operands) nor a reload of a spilled scalar, and does one multiplication and one exclusive-or fewer.
+// The arithmetic is philox4x32_10's, word for word.
+struct PhiloxUniform {
+    uint32_t r1_n2;   // c3 ^ k1
+    uint32_t r2_n0;   // lo(M1 * c2) ^ (k0 + W0)
+    uint32_t r2_n2;   // hi(M0 * n0) ^ (k1 + W1)
+    uint32_t r3_n2;   // lo(M0 * n0) ^ (k1 + 2 W1)
+};
+__device__ __forceinline__ PhiloxUniform philox_uniform(const uint32_t c1, const uint32_t c2, const uint32_t c3, const uint32_t k0, const uint32_t k1) {
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint64_t q0 = (uint64_t)0xD2511F53u * n0;
+    PhiloxUniform u;
+    u.r1_n2 = opaque(c3 ^ k1);
+    u.r2_n0 = opaque((uint32_t)p1 ^ (k0 + 0x9E3779B9u));
+    u.r2_n2 = opaque((uint32_t)(q0 >> 32) ^ (k1 + 0xBB67AE85u));
+    u.r3_n2 = opaque((uint32_t)q0 ^ (k1 + 2u * 0xBB67AE85u));
+    return u;
+}
+// ... and the block of counter (c0, c1, c2, c3) for the per-lane c0
+template <bool OWN_KEYS = true>
+__device__ __forceinline__ U4 philox4x32_10_lane(const uint32_t c0_, const PhiloxUniform& u, uint32_t k0, uint32_t k1) {
+#ifndef SGW_DIAG_SHARED_KEYS
+    if constexpr (OWN_KEYS) asm volatile("" : "+s"(k0), "+s"(k1));
+#endif
+    // round 1: p1 and n0 are uniform
+    const uint64_t a0 = (uint64_t)0xD2511F53u * c0_;
+    const uint32_t a_n2 = (uint32_t)(a0 >> 32) ^ u.r1_n2;
+    // round 2: c0 = n0 (uniform: its product is in u), c1 = lo(p1) (uniform), c2 = a_n2, c3 = lo(a0)
+    const uint64_t b1 = (uint64_t)0xCD9E8D57u * a_n2;
+    const uint32_t b_n0 = (uint32_t)(b1 >> 32) ^ u.r2_n0;
+    const uint32_t b_n2 = (uint32_t)a0 ^ u.r2_n2;
+    // round 3: c0 = b_n0, c1 = lo(b1), c2 = b_n2, c3 = lo(M0 * n0) (uniform)
+    k0 += 2u * 0x9E3779B9u;
+    k1 += 2u * 0xBB67AE85u;
+    const uint64_t d0 = (uint64_t)0xD2511F53u * b_n0;
+    const uint64_t d1 = (uint64_t)0xCD9E8D57u * b_n2;
+    uint32_t c0 = xor3((uint32_t)(d1 >> 32), (uint32_t)b1, k0);
+    uint32_t c2 = (uint32_t)(d0 >> 32) ^ u.r3_n2;
+    uint32_t c1 = (uint32_t)d1, c3 = (uint32_t)d0;
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+    }
+    return U4{c0, c1, c2, c3};
+}
+
 __device__ __forceinline__ uint32_t word_of(const U4& v, int i) {
     return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
 }
@@ -270,6 +330,59 @@ __device__ __forceinline__ void gsync() {
         __builtin_amdgcn_wave_barrier();
     } else {
         __syncthreads();
+    }
+}
+
+// a compile-time flag as a value: selects the instance of a generic lambda
+template <bool B>
+struct BoolC {
+    static constexpr bool value = B;
+};
+
+// ---------------------------------------------------------------- burst emit
+// Staged dwords [i0, i1) of a line-aligned span leave as streaming stores, one wave-wide store per 64 dwords: `line` (wave-uniform) is
+// where dword 0 of the span goes and sits on a 128-byte line, so lane 0 of every store does; load(i) returns the four staged bytes
+// of span dword i.  F32: a dword leaves as four floats (tof(byte) each: 16 bytes per lane, eight whole lines per store), else as it is.
+// The trip count is wave-uniform and the destination a scalar base that advances by scalar adds, next to the lane's fixed offset:
+// only the first iteration (idle low lanes, i < i0) and the last (ragged end, i >= i1) are masked; the ones between are a
+// ds_read_b32, the converts and the store -- no compare, no 64-bit vector add, no exec bookkeeping.
+template <bool F32, class Load, class ToF>
+__device__ __forceinline__ void burst_emit(void* const line, const int i0, const int i1, const int lane, Load load, ToF tof) {
+    typedef float vfloat4 __attribute__((ext_vector_type(4)));
+    constexpr uint32_t kElem = F32 ? 16u : 4u;
+    if (i1 <= i0) return;
+    const int k0 = i0 >> 6, k1 = (i1 + 63) >> 6;          // iterations [k0, k1): k0 is the first, k1 - 1 the last
+    uint32_t voff = (uint32_t)lane * kElem;
+    char* base = static_cast<char*>(line) + (int64_t)k0 * (int64_t)(64u * kElem);
+    auto one = [&](const int i) {
+        const uint32_t b = load(i);
+        asm volatile("" : "+v"(voff));   // (keeps the zero-extension next to the store: scalar base + the lane's 32-bit offset is the store's scalar-base form)
+        if constexpr (F32) {
+            vfloat4 v;
+            v.x = tof(b & 0xFFu);
+            v.y = tof((b >> 8) & 0xFFu);
+            v.z = tof((b >> 16) & 0xFFu);
+            v.w = tof(b >> 24);
+#ifdef SGW_DIAG_PLAIN_STORES
+            *reinterpret_cast<vfloat4*>(base + voff) = v;
+#else
+            __builtin_nontemporal_store(v, reinterpret_cast<vfloat4*>(base + voff));
+#endif
+        } else {
+            __builtin_nontemporal_store(b, reinterpret_cast<uint32_t*>(base + voff));
+        }
+    };
+    const int first = 64 * k0 + lane;
+    if (first >= i0 && first < i1) one(first);
+#pragma unroll 1
+    for (int k = k0 + 1; k < k1 - 1; ++k) {
+        base += 64u * kElem;
+        one(64 * k + lane);
+    }
+    if (k1 - 1 > k0) {
+        base += 64u * kElem;
+        const int last = 64 * (k1 - 1) + lane;
+        if (last < i1) one(last);
     }
 }
 

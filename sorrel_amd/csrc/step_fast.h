@@ -31,8 +31,8 @@ constexpr size_t kCacheResidentGrid = (size_t)288 << 20;   // on-die capacity: 2
 // The spawner test is a byte compare per cell (the compiler emits it as ONE v_cmp with a byte select on the dword) and meets the
 // draw's compare as lane masks in scalar registers; until round 4 a byte-parallel match produced 0x80 flags that every cell then
 // tested again in vector registers (24 + 5.5 vector instructions per dword against 16 now; the kernel is vector-issue bound).
-template <bool OWN_KEYS>
-__device__ __forceinline__ uint32_t sweep_hits(const uint4& u, const uint32_t unit, const Params& p, const uint32_t env_id, const uint32_t turn, const uint32_t ep4) {
+template <class Draw>
+__device__ __forceinline__ uint32_t sweep_hits_with(const uint4& u, const Params& p, Draw draw) {   // draw(k): the Philox block of the unit's dword k
     uint32_t hits = 0;
     const uint32_t pat = p.spawn_pat & 0xFFu;
 #pragma unroll
@@ -40,7 +40,7 @@ __device__ __forceinline__ uint32_t sweep_hits(const uint4& u, const uint32_t un
         const uint32_t dv = k == 0 ? u.x : k == 1 ? u.y : k == 2 ? u.z : u.w;
         const bool m0 = (dv & 0xFFu) == pat, m1 = ((dv >> 8) & 0xFFu) == pat, m2 = ((dv >> 16) & 0xFFu) == pat, m3 = (dv >> 24) == pat;
         if (m0 | m1 | m2 | m3) {
-            const U4 w = philox4x32_10<OWN_KEYS>(opaque(unit * 4 + k), turn, env_id, ep4 | SGW_STREAM_SPAWN, p.seed_lo, p.seed_hi);
+            const U4 w = draw(k);
             const bool f = p.spawn_full != 0;
             uint32_t hb = 0;
             hb |= (m0 && (f || w.x < p.spawn_thr)) ? 1u : 0u;
@@ -51,6 +51,15 @@ __device__ __forceinline__ uint32_t sweep_hits(const uint4& u, const uint32_t un
         }
     }
     return hits;
+}
+template <bool OWN_KEYS>
+__device__ __forceinline__ uint32_t sweep_hits(const uint4& u, const uint32_t unit, const Params& p, const uint32_t env_id, const uint32_t turn, const uint32_t ep4) {
+    return sweep_hits_with(u, p, [&](const int k) { return philox4x32_10<OWN_KEYS>(opaque(unit * 4 + k), turn, env_id, ep4 | SGW_STREAM_SPAWN, p.seed_lo, p.seed_hi); });
+}
+// ... with the wave-uniform part of the blocks computed once per wave and turn (common.h: philox_uniform)
+template <bool OWN_KEYS>
+__device__ __forceinline__ uint32_t sweep_hits(const uint4& u, const uint32_t unit, const Params& p, const PhiloxUniform& pu) {
+    return sweep_hits_with(u, p, [&](const int k) { return philox4x32_10_lane<OWN_KEYS>(opaque(unit * 4 + k), pu, p.seed_lo, p.seed_hi); });
 }
 
 // Rare second draw: what spawns in each hit cell; written straight into the LDS grid.
@@ -142,16 +151,8 @@ __device__ __forceinline__ void fast_rows_emit(const Params& p, const RowPtrs* r
         if ((kN & 1) == 0 && (ad & 15u) == 0) {
             const int q = T >> 2;
             const int mis = (int)((ad >> 4) & 7u);
-            for (int i = lane - mis; i < q; i += 64) {
-                if (i < 0) continue;
-                const uint32_t lo = src16(2 * i), hi = src16(2 * i + 1);
-                vfloat4 v;
-                v.x = (float)(lo & 0xFFu);
-                v.y = (float)(lo >> 8);
-                v.z = (float)(hi & 0xFFu);
-                v.w = (float)(hi >> 8);
-                __builtin_nontemporal_store(v, reinterpret_cast<vfloat4*>(dst) + i);
-            }
+            burst_emit<true>(reinterpret_cast<vfloat4*>(dst) - mis, mis, mis + q, lane,
+                             [&](const int i) { return src16(2 * (i - mis)) | (src16(2 * (i - mis) + 1) << 16); }, [](const uint32_t k) { return (float)k; });
             if ((T & 3) && lane == 0) {                   // (an odd number of envs of an odd kN / 2: two floats behind the last float4)
                 const uint32_t b = src16(2 * q);
                 vfloat2 v;
@@ -451,11 +452,12 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                 for (int k = 0; k < NU; ++k)
                     if (lane + 64 * k < nunits) u[k] = lg16[lane + 64 * k];
             }
+            const PhiloxUniform pu = philox_uniform(turn, env_id, ep4 | SGW_STREAM_SPAWN, p.seed_lo, p.seed_hi);
 #pragma unroll
             for (int k = 0; k < NU; ++k) {
                 hits[k] = 0;
                 if ((k < kFullRounds || !kTailDword) && lane + 64 * k < nunits && do_sweep)
-                    hits[k] = sweep_hits<kOwnKeys>(u[k], (uint32_t)(lane + 64 * k), p, env_id, turn, ep4);
+                    hits[k] = sweep_hits<kOwnKeys>(u[k], (uint32_t)(lane + 64 * k), p, pu);
             }
             gsync<1>();
             if (do_sweep) {
@@ -599,7 +601,6 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
         // waves), element-wise where they do not fill a float4.
         [[maybe_unused]] auto emit_chunk = [&](const int a_lo, const int a_hi, const bool last) {
             gsync<1>();
-            typedef float vfloat4 __attribute__((ext_vector_type(4)));
             const int N = (a_hi - a_lo) * C * VV;
             const int64_t e0 = turn_obs + (env * p.A + a_lo) * (int64_t)(C * VV);
             const int sh = (int)ch_shift, lo = (int)ch_lo;
@@ -616,20 +617,7 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             const bool edge = lane == 0 ? (lo & 3) != 0 : (lane == 1 && (he & 3) != 0 && (i1 >= i0 || (lo & 3) == 0));
             if (ROWX || !p.obs_u8) {
                 float* gb = ROWX ? row_dst - sh : p.obs + (e0 - sh);
-                for (int i = lane; i < i1; i += 64) {
-                    if (i < i0) continue;
-                    const uint32_t b = ob4[i];
-                    vfloat4 v;
-                    v.x = tof(b & 0xFFu);
-                    v.y = tof((b >> 8) & 0xFFu);
-                    v.z = tof((b >> 16) & 0xFFu);
-                    v.w = tof(b >> 24);
-#ifdef SGW_DIAG_PLAIN_STORES
-                    *reinterpret_cast<vfloat4*>(gb + 4 * i) = v;
-#else
-                    __builtin_nontemporal_store(v, reinterpret_cast<vfloat4*>(gb + 4 * i));
-#endif
-                }
+                burst_emit<true>(gb, i0, i1, lane, [&](const int i) { return ob4[i]; }, tof);
                 if (edge) {
                     const uint32_t b = ob4[ie];
 #pragma unroll
@@ -638,10 +626,7 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                 }
             } else {
                 uint8_t* gb = reinterpret_cast<uint8_t*>(p.obs) + (e0 - sh);
-                for (int i = lane; i < i1; i += 64) {
-                    if (i < i0) continue;
-                    __builtin_nontemporal_store(ob4[i], reinterpret_cast<uint32_t*>(gb + 4 * i));
-                }
+                burst_emit<false>(gb, i0, i1, lane, [&](const int i) { return ob4[i]; }, tof);
                 if (edge) {
                     const uint32_t b = ob4[ie];
 #pragma unroll
@@ -681,25 +666,21 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             for (int q = 0; q < NW; ++q) fill_v[q] = opaque(p.fill_delta[q]);
         }
         // ---- agents, strictly in list order (SGW_STEP_OBS_NEXT: one extra, observe-only iteration for agent a1)
-        const int a_end = (p.obs_next && p.a1 < p.A) ? p.a1 + 1 : p.a1;
-        for (int a = p.a0; a < a_end; ++a) {
-            if constexpr (ROWX) {                    // a chunk = one agent = one row: the agent before leaves, this one's row sets the staging offset
-                if (a > p.a0 && write_obs) emit_chunk(a - 1, a, true);
-                ch_a0 = a;
-                row_dst = static_cast<float*>(rp->p[a]) + env * rp->stride;
-                ch_lo = ch_shift = (uint32_t)(reinterpret_cast<uintptr_t>(row_dst) >> 2) & kLineMask;
-            } else if constexpr (kStageAlways) {
-                if (a - ch_a0 == p.stage_agents) {   // the staging area is full: out with it, start the next chunk
-                    if (write_obs) emit_chunk(ch_a0, a, false);   // (moves ch_shift / ch_lo on to the next chunk)
-                    ch_a0 = a;
-                }
-            }
-            const uint32_t yx_a = (uint32_t)__builtin_amdgcn_readlane((int)yx, a);   // (one lane read: row, column and own cell follow in scalar registers)
-            const int y = (int)(yx_a & 0xFFu), x = (int)(yx_a >> 8);
-            const int s_o = zoff + y * W + x;
-            if (p.obs_next ? a == p.a1 : write_obs) {
+        // An agent's window as one body with two instances.  LEAN: a launch that stages whole envs, writes observations and has no obs_next -- the
+        // gather into the staging area and nothing else: none of the unstaged path's tests, store branches and global pointer, all of them
+        // launch-uniform and re-evaluated by every iteration before.  Which instance a launch runs is decided once, in front of the loop; the
+        // sequential resolve behind the window stays ONE piece of code for both (the reward total is one v_add_f64 in the kernel).
+        constexpr bool kVersioned = ONEHOT && kStatic && !kStageAlways && !TAG && !RULES && !ROWS && !MULTI;
+        const bool lean = kVersioned && stage && write_obs && !p.obs_next;
+        auto window = [&](const int a, const int y, const int x, const int s_o, auto lean_c) {
+            constexpr bool LEAN = decltype(lean_c)::value;
+            {
                 const int cbase = s_o - zoff;
-                float* obase = p.obs + turn_obs + ((env * p.obs_A + (a - p.obs_a0)) * (int64_t)C) * VV;
+                // (the direct stores' base from the agent's number as a scalar of this iteration: as an induction variable it is a 64-bit vector
+                // add per iteration, which the launches that stage paid as well)
+                int a_s = a;
+                if constexpr (kVersioned && !LEAN) asm volatile("" : "+s"(a_s));
+                [[maybe_unused]] float* obase = p.obs + turn_obs + ((env * p.obs_A + (a_s - p.obs_a0)) * (int64_t)C) * VV;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     if (64 * k >= VV) break;
@@ -710,7 +691,7 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
 #endif
                         const bool inb = (unsigned)(y + wdi[k]) < (unsigned)H && (unsigned)(x + wdj[k]) < (unsigned)W;
                         const int off = inb ? cbase + woff[k] : 0;   // clamped: the read is always in range
-                        float* o = obase + w;
+                        [[maybe_unused]] float* o = obase + w;
                         if constexpr (ONEHOT) {
                             uint32_t cnt[NW];
 #pragma unroll
@@ -736,7 +717,7 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                                 else if constexpr (I16) return min((cnt[c >> 1] >> (16 * (c & 1))) & 0xFFFFu, 255u);
                                 else return (cnt[c >> 2] >> (8 * (c & 3))) & 0xFFu;
                             };
-                            if (stage) {
+                            if (LEAN || stage) {
                                 uint8_t* os = ob + (kStageAlways ? (int)ch_shift + ((a - ch_a0) * C) * VV : (a * C) * VV) + w;
                                 if constexpr (TC != 0) {
 #pragma unroll
@@ -776,6 +757,28 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                         }
                     }
                 }
+            }
+        };
+        const int a_end = (p.obs_next && p.a1 < p.A) ? p.a1 + 1 : p.a1;
+        for (int a = p.a0; a < a_end; ++a) {
+            if constexpr (ROWX) {                    // a chunk = one agent = one row: the agent before leaves, this one's row sets the staging offset
+                if (a > p.a0 && write_obs) emit_chunk(a - 1, a, true);
+                ch_a0 = a;
+                row_dst = static_cast<float*>(rp->p[a]) + env * rp->stride;
+                ch_lo = ch_shift = (uint32_t)(reinterpret_cast<uintptr_t>(row_dst) >> 2) & kLineMask;
+            } else if constexpr (kStageAlways) {
+                if (a - ch_a0 == p.stage_agents) {   // the staging area is full: out with it, start the next chunk
+                    if (write_obs) emit_chunk(ch_a0, a, false);   // (moves ch_shift / ch_lo on to the next chunk)
+                    ch_a0 = a;
+                }
+            }
+            const uint32_t yx_a = (uint32_t)__builtin_amdgcn_readlane((int)yx, a);   // (one lane read: row, column and own cell follow in scalar registers)
+            const int y = (int)(yx_a & 0xFFu), x = (int)(yx_a >> 8);
+            const int s_o = zoff + y * W + x;
+            if (lean) {
+                if constexpr (kVersioned) window(a, y, x, s_o, BoolC<true>{});
+            } else if (p.obs_next ? a == p.a1 : write_obs) {
+                window(a, y, x, s_o, BoolC<false>{});
             }
             if (!p.do_move || a >= p.a1) continue;
             // ---- the sequential part (agent.py:219-221, gridworld.py:110-122): scalar
@@ -935,19 +938,12 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                 // of a line costs as if ... tools/micro/region_writer.hip: 1 KiB stores shifted by 64 / 32 / 16 bytes write at
                 // 4.91 / 4.44 / 4.44 TB/s against 5.48 aligned.  mis = float4s between the line and the env's first element.
                 const int mis = (int)((reinterpret_cast<uintptr_t>(o4) >> 4) & 7u);
-                for (int i = lane - mis; i < nd; i += 64) {
-                    if (i < 0) continue;
-                    const uint32_t b = ob4[i];
-                    vfloat4 v;
-                    v.x = (float)(b & 0xFFu);
-                    v.y = (float)((b >> 8) & 0xFFu);
-                    v.z = (float)((b >> 16) & 0xFFu);
-                    v.w = (float)(b >> 24);
-                    __builtin_nontemporal_store(v, &o4[i]);
-                }
+                burst_emit<true>(o4 - mis, mis, mis + nd, lane, [&](const int i) { return ob4[i - mis]; }, [](const uint32_t k) { return (float)k; });
             } else {
+                // the compact format: two whole lines per wave instruction, lane 0 on a line as well (mis = dwords between the line and the env's first)
                 uint32_t* o1 = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(p.obs) + turn_obs + env * (int64_t)(p.A * C * VV));
-                for (int i = lane; i < nd; i += 64) __builtin_nontemporal_store(ob4[i], &o1[i]);   // two whole lines per wave instruction
+                const int mis = (int)((reinterpret_cast<uintptr_t>(o1) >> 2) & 31u);
+                burst_emit<false>(o1 - mis, mis, mis + nd, lane, [&](const int i) { return ob4[i - mis]; }, [](const uint32_t k) { return (float)k; });
             }
         }
         if (p.do_move && mine) {      // this turn's rewards (and what TagAgent.pov appends)
