@@ -107,6 +107,7 @@ extern "C" {
 #define SGW_STREAM_EXPLORE 7           /* index = agent: the epsilon test of SGW_ACT_QF32 (sgw_turn_epsilon) */
 #define SGW_STREAM_VALUE 8             /* index = layer-major cell index of the TARGET cell (the spawn stream's index), turn = the turn in
                                         * flight: which of its two values a type with value_alt_prob > 0 is worth this turn */
+#define SGW_STREAM_SAMPLE 9            /* sgw_sample's drawn indices: epoch 0, turn / env = the low / high word of the draw counter */
 
 /* what Agent.act does (sgw_config.agent_rule) */
 #define SGW_AGENT_RULE_MOVE 0 /* MovingAgent.act: reward = value of the target, then move (sorrel/agents/agent.py:215-225) */
@@ -598,6 +599,52 @@ typedef struct sgw_render_desc {
 } sgw_render_desc;
 /* Asynchronous on `stream`.  Bad shapes: SGW_EINVAL with the reason in sgw_last_error(). */
 int sgw_render(const sgw_render_desc* desc, void* stream);
+
+/* ---- replay batches (sorrel/buffers.py:98-124: Buffer.sample, for a ring that holds every env, on the device) ----
+ * One launch gathers n frame-stacked samples from a replay ring: for sample k with (t, e) = (start, env),
+ *     out_states[k]      = rows t .. t + n_frames - 1 of env e, concatenated          (uint8 rows widen exactly: (float)byte)
+ *     out_next_states[k] = rows t + 1 .. t + n_frames
+ *     out_actions / out_rewards / out_dones [k] = the scalars of row t + n_frames - 1
+ *     out_valid[k]       = 1 - (any dones[t .. t + n_frames - 2][e] != 0)
+ * Row (t, e) of `states` starts at element t * state_turn_stride + e * state_env_stride; actions, rewards and dones share the two
+ * scalar strides in the same way -- so a Buffer ([capacity][E][R]: strides E * R / R and E / 1), one agent of a TurnBuffer
+ * ([capacity][E][A][R]: pointers offset by a * R and a, strides E * A * R / A * R and E * A / A) and every agent of one (num_envs =
+ * E * A, strides E * A * R / R and E * A / 1) are all read where they lie.  Every source row is read once (n_frames + 1 rows per sample).
+ * starts == envs == NULL: the call draws its indices from the engine's counter RNG, stream SGW_STREAM_SAMPLE.  With c = *draw_count
+ * (or `draw` when draw_count is NULL), sample k takes u32 number 2k (start) and 2k + 1 (env) of
+ *     Philox4x32-10(ctr = {index >> 2, c & 0xffffffff, c >> 32, SGW_STREAM_SAMPLE}, key = {seed lo, seed hi}),
+ * start = (u * num_starts) >> 32, env = (u * num_envs) >> 32.  Draws are WITH replacement over (turn, env) pairs; the reference's
+ * replace=False holds for its population of one env's turns, which a batch over many envs leaves behind.  A given draw_count is
+ * incremented by one after the gather (same stream), so a recorded graph draws a fresh batch at every replay.
+ * A GIVEN index outside [0, num_starts) / [0, num_envs) leaves that sample's outputs unwritten.  Needs no engine; all pointers are
+ * device pointers. */
+#define SGW_SAMPLE_F32 0         /* src_type: the ring's rows are float32 */
+#define SGW_SAMPLE_U8 1          /* ... uint8 (the compact observation format) */
+#define SGW_SAMPLE_ACT_I64 0     /* act_type: the ring's actions are int64 (Buffer) */
+#define SGW_SAMPLE_ACT_U8 1      /* ... uint8 (TurnBuffer) */
+typedef struct sgw_sample_desc {
+    const void* states;          /* ring of observation rows, element type src_type */
+    const void* actions;         /* act_type */
+    const float* rewards;
+    const float* dones;
+    const int64_t* starts;       /* [n] first frame (ring row) of each sample, or NULL: draw */
+    const int64_t* envs;         /* [n] env of each sample; NULL exactly when starts is */
+    uint64_t* draw_count;        /* device counter [1] read by the draw and incremented after it, or NULL: `draw` is used */
+    float* out_states;           /* [n][n_frames * row_elems] */
+    float* out_next_states;      /* [n][n_frames * row_elems] */
+    int64_t* out_actions;        /* [n] */
+    float* out_rewards;          /* [n] */
+    float* out_dones;            /* [n] */
+    float* out_valid;            /* [n] */
+    int64_t* out_index;          /* [n][2] = (start, env) used, or NULL */
+    int64_t n, capacity, num_envs, num_starts, row_elems;     /* num_starts + n_frames <= capacity; num_starts, num_envs < 2^31; row_elems < 2^30 */
+    int64_t state_turn_stride, state_env_stride;              /* in elements */
+    int64_t scalar_turn_stride, scalar_env_stride;            /* in elements: actions, rewards, dones */
+    uint64_t seed, draw;
+    int32_t n_frames, src_type, act_type, reserved;           /* reserved: 0 */
+} sgw_sample_desc;
+/* Asynchronous on `stream`.  Bad arguments: SGW_EINVAL with the reason in sgw_last_error(), before anything is launched. */
+int sgw_sample(const sgw_sample_desc* desc, void* stream);
 
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */

@@ -25,6 +25,9 @@ TAIL_NONE, TAIL_AGENT_IS_IT, TAIL_POSITION_TABLE = 0, 1, 2
 OK, EINVAL, EHIP, ENOMEM = 0, -1, -2, -3
 RENDER_COMPOSITE, RENDER_LAYERS = 0, 1
 TILE_OPAQUE, TILE_CLEAR, TILE_KEEP = 1, 2, 0xFFFF
+STREAM_SAMPLE = 9           # sgw_sample's drawn (start, env) pairs: epoch 0, turn / env slots = low / high word of the draw counter
+SAMPLE_F32, SAMPLE_U8 = 0, 1
+SAMPLE_ACT_I64, SAMPLE_ACT_U8 = 0, 1
 
 
 class SgwConfig(C.Structure):
@@ -120,6 +123,22 @@ class SgwRenderDesc(C.Structure):
     ]
 
 
+class SgwSampleDesc(C.Structure):
+    """Mirror of ``struct sgw_sample_desc`` (include/sgw.h): one ``sgw_sample`` call."""
+
+    _fields_ = [
+        ("states", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+        ("starts", C.c_void_p), ("envs", C.c_void_p), ("draw_count", C.c_void_p),
+        ("out_states", C.c_void_p), ("out_next_states", C.c_void_p), ("out_actions", C.c_void_p),
+        ("out_rewards", C.c_void_p), ("out_dones", C.c_void_p), ("out_valid", C.c_void_p), ("out_index", C.c_void_p),
+        ("n", C.c_int64), ("capacity", C.c_int64), ("num_envs", C.c_int64), ("num_starts", C.c_int64), ("row_elems", C.c_int64),
+        ("state_turn_stride", C.c_int64), ("state_env_stride", C.c_int64),
+        ("scalar_turn_stride", C.c_int64), ("scalar_env_stride", C.c_int64),
+        ("seed", C.c_uint64), ("draw", C.c_uint64),
+        ("n_frames", C.c_int32), ("src_type", C.c_int32), ("act_type", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -130,7 +149,7 @@ EXPORTS = (
     "sgw_algorithmic_bytes_per_env_step", "sgw_set_timing", "sgw_get_step_time_ms", "sgw_get_step_times_ms",
     "sgw_set_auto_reset", "sgw_set_wg_per_cu", "sgw_launch_info", "sgw_capabilities", "sgw_observe_rows", "sgw_act", "sgw_observe_full",
     "sgw_set_option", "sgw_plan", "sgw_jit_stats", "sgw_jit_compile", "sgw_bind_row_tail",
-    "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render",
+    "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render", "sgw_sample",
     "sgw_last_error", "sgw_version",
 )
 
@@ -268,6 +287,8 @@ def load():
     lib.sgw_turn_epsilon.restype = C.c_int
     lib.sgw_render.argtypes = [C.POINTER(SgwRenderDesc), vp]
     lib.sgw_render.restype = C.c_int
+    lib.sgw_sample.argtypes = [C.POINTER(SgwSampleDesc), vp]
+    lib.sgw_sample.restype = C.c_int
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

@@ -16,6 +16,122 @@ import torch
 from sorrel_amd.spec import resolve_device
 
 
+def _stack_torch(states, actions, rewards, dones, n_frames: int, batch_size: int, t0, e):
+    """The reference's stacking (``sorrel/buffers.py:109-122``) over a ring ``[capacity, N, ...]`` by torch indexing."""
+    device = states.device
+    t0 = torch.as_tensor(t0, dtype=torch.long)
+    e = torch.as_tensor(e, dtype=torch.long).to(device)
+    idx = (t0.cpu()[:, None] + torch.arange(n_frames)[None, :]).to(device)        # [B, n_frames]
+    ee = e[:, None].expand_as(idx)
+    src = states[idx, ee].reshape(batch_size, -1)
+    nxt = states[idx + 1, ee].reshape(batch_size, -1)
+    last = idx[:, -1]
+    acts = actions[last, e].reshape(batch_size, -1)
+    rews = rewards[last, e].reshape(batch_size, -1)
+    dns = dones[last, e].reshape(batch_size, -1)
+    valid = (1.0 - (dones[idx[:, :-1], ee[:, :-1]] != 0).any(dim=-1).float()).reshape(batch_size, -1)
+    return src, acts, rews, nxt, dns, valid
+
+
+def _ring_layout(ring, agent):
+    """What ``sgw_sample`` needs to read a ring where it lies: base pointers, the number of (env) columns, the row length, the
+    (turn, env) strides of the rows and of the scalars, and the element types (include/sgw.h)."""
+    from sorrel_amd import _native as N
+
+    if isinstance(ring, TurnBuffer):
+        E, A = ring.num_envs, ring.obs_shape[0]
+        R = int(np.prod(ring.obs_shape[1:]))
+        if ring.obs.dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"sgw_sample reads float32 or uint8 observations, not {ring.obs.dtype}")
+        src = N.SAMPLE_U8 if ring.obs.dtype == torch.uint8 else N.SAMPLE_F32
+        tensors = (ring.obs, ring.actions, ring.rewards, ring.dones)
+        if agent is None:
+            cols, offs, sstr, cstr = E * A, (0, 0), (E * A * R, R), (E * A, 1)
+        else:
+            if not 0 <= int(agent) < A:
+                raise IndexError(f"agent {agent} outside [0, {A})")
+            cols, offs, sstr, cstr = E, (int(agent) * R, int(agent)), (E * A * R, A * R), (E * A, A)
+        act = N.SAMPLE_ACT_U8
+    else:
+        if agent is not None:
+            raise ValueError("a Buffer holds one agent: agent must be None")
+        E, R = ring.num_envs, int(np.prod(ring.obs_shape))
+        tensors = (ring.states, ring.actions, ring.rewards, ring.dones)
+        cols, offs, sstr, cstr = E, (0, 0), (E * R, R), (E, 1)
+        src, act = N.SAMPLE_F32, N.SAMPLE_ACT_I64
+    for t in tensors:
+        if not t.is_contiguous():
+            raise ValueError("sgw_sample reads contiguous rings")
+    st, ac, rw, dn = tensors
+    ptrs = (st.data_ptr() + offs[0] * st.element_size(), ac.data_ptr() + offs[1] * ac.element_size(),
+            rw.data_ptr() + offs[1] * 4, dn.data_ptr() + offs[1] * 4)
+    return dict(ptrs=ptrs, cols=cols, R=R, sstr=sstr, cstr=cstr, src=src, act=act, capacity=ring.capacity, device=ring.device)
+
+
+def _check_index_list(name, values, batch_size, bound, device):
+    """A caller's index list: host values are range-checked (``IndexError``), device tensors passed through as they are."""
+    if torch.is_tensor(values) and values.device.type == "cuda":
+        out = values.to(device=device, dtype=torch.long).contiguous()
+        if out.numel() != batch_size:
+            raise ValueError(f"{name}: {out.numel()} indices for a batch of {batch_size}")
+        return out
+    host = np.asarray(values.cpu() if torch.is_tensor(values) else values).astype(np.int64).reshape(-1)
+    if host.size != batch_size:
+        raise ValueError(f"{name}: {host.size} indices for a batch of {batch_size}")
+    if host.size and (host.min() < 0 or host.max() >= bound):
+        raise IndexError(f"{name}: index outside [0, {bound})")
+    return host
+
+
+def _launch_sample(layout, n_frames, batch_size, outs, index, starts, envs, num_starts, count=None, seed=0):
+    """One ``sgw_sample`` call on the current stream.  ``outs`` = (states, next_states, actions, rewards, dones, valid) tensors."""
+    import ctypes as C
+
+    from sorrel_amd import _native as N
+
+    d = N.SgwSampleDesc()
+    d.states, d.actions, d.rewards, d.dones = layout["ptrs"]
+    if starts is not None:
+        d.starts, d.envs = starts.data_ptr(), envs.data_ptr()
+    if count is not None:
+        d.draw_count = count.data_ptr()
+    d.out_states, d.out_next_states, d.out_actions, d.out_rewards, d.out_dones, d.out_valid = (t.data_ptr() for t in outs)
+    if index is not None:
+        d.out_index = index.data_ptr()
+    d.n, d.capacity, d.num_envs, d.num_starts, d.row_elems = batch_size, layout["capacity"], layout["cols"], num_starts, layout["R"]
+    d.state_turn_stride, d.state_env_stride = layout["sstr"]
+    d.scalar_turn_stride, d.scalar_env_stride = layout["cstr"]
+    d.seed, d.draw = seed & 0xFFFFFFFFFFFFFFFF, 0
+    d.n_frames, d.src_type, d.act_type = n_frames, layout["src"], layout["act"]
+    N.check(N.load().sgw_sample(C.byref(d), C.c_void_p(torch.cuda.current_stream(layout["device"]).cuda_stream)))
+
+
+def _sample_outputs(batch_size, n_frames, R, device):
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.empty((batch_size, n_frames * R), **f32), torch.empty((batch_size, n_frames * R), **f32),
+            torch.empty((batch_size, 1), dtype=torch.int64, device=device), torch.empty((batch_size, 1), **f32),
+            torch.empty((batch_size, 1), **f32), torch.empty((batch_size, 1), **f32))
+
+
+def _sample_fresh(layout, n_frames, batch_size, t0, e, num_starts):
+    """Host-side indices -> one upload -> ``sgw_sample`` into freshly allocated tensors (``Buffer.sample`` / ``TurnBuffer.sample``
+    on a device ring): the caller keeps the results."""
+    device = layout["device"]
+    t0 = _check_index_list("starts", t0, batch_size, num_starts, device)
+    e = _check_index_list("envs", e, batch_size, layout["cols"], device)
+    if isinstance(t0, np.ndarray) and isinstance(e, np.ndarray):
+        both = torch.from_numpy(np.stack([t0, e])).to(device)
+        t0, e = both[0], both[1]
+    else:
+        t0 = torch.from_numpy(t0).to(device) if isinstance(t0, np.ndarray) else t0
+        e = torch.from_numpy(e).to(device) if isinstance(e, np.ndarray) else e
+    outs = _sample_outputs(batch_size, n_frames, layout["R"], device)
+    if batch_size:
+        _launch_sample(layout, n_frames, batch_size, outs, None, t0, e, num_starts)
+    s, ns, a, r, dn, v = outs
+    return s, a, r, ns, dn, v
+
+
 class Buffer:
     """``extra`` keyword arguments declare additional int64 columns exactly as in the reference
     (``Buffer(capacity, obs_shape, positions=(2,))``, ``sorrel/buffers.py:39-44``): a tuple gives the trailing
@@ -202,23 +318,35 @@ class Buffer:
         sel = [(self.idx - k + j) % self.capacity for j in range(k)]
         return self.states[sel]
 
+    def _draw(self, batch_size: int, starts, envs):
+        """The host's draws (or the caller's indices): ``starts`` before ``envs``, from torch's global generator."""
+        hi = max(1, self.size - self.n_frames - 1)
+        t0 = torch.randint(0, hi, (batch_size,)) if starts is None else starts
+        e = torch.randint(0, self.num_envs, (batch_size,)) if envs is None else envs
+        return t0, e
+
+    def _sample_torch(self, batch_size: int, starts=None, envs=None):
+        """``sample`` by torch indexing: the CPU path, and what the device path is compared with and timed against."""
+        t0, e = self._draw(batch_size, starts, envs)
+        return _stack_torch(self.states, self.actions, self.rewards, self.dones, self.n_frames, batch_size, t0, e)
+
     def sample(self, batch_size: int, starts=None, envs=None):
         """Uniform sample of (turn, env) pairs with ``n_frames`` stacking:
         states, actions, rewards, next_states, dones, valid (``sorrel/buffers.py:98-124``).
-        ``starts`` / ``envs`` override the random draws (first frame index and env of each sample)."""
-        hi = max(1, self.size - self.n_frames - 1)
-        t0 = torch.randint(0, hi, (batch_size,)) if starts is None else torch.as_tensor(starts, dtype=torch.long)
-        e = (torch.randint(0, self.num_envs, (batch_size,)) if envs is None else torch.as_tensor(envs, dtype=torch.long)).to(self.device)
-        idx = (t0[:, None] + torch.arange(self.n_frames)[None, :]).to(self.device)        # [B, n_frames]
-        ee = e[:, None].expand_as(idx)
-        states = self.states[idx, ee].reshape(batch_size, -1)
-        next_states = self.states[idx + 1, ee].reshape(batch_size, -1)
-        last = idx[:, -1]
-        actions = self.actions[last, e].reshape(batch_size, -1)
-        rewards = self.rewards[last, e].reshape(batch_size, -1)
-        dones = self.dones[last, e].reshape(batch_size, -1)
-        valid = (1.0 - (self.dones[idx[:, :-1], ee[:, :-1]] != 0).any(dim=-1).float()).reshape(batch_size, -1)
-        return states, actions, rewards, next_states, dones, valid
+        ``starts`` / ``envs`` override the random draws (first frame index and env of each sample).
+        On a HIP device the batch is gathered by one ``sgw_sample`` launch into freshly allocated tensors.  There, indices the caller
+        gives may name any row whose stacked frames lie inside the ring -- ``0 <= start < capacity - n_frames`` (not the size-based
+        bound of the draws, ``max(1, size - n_frames - 1)``, which ``ReplaySampler`` also applies to given indices) and
+        ``0 <= env < num_envs``: a host list outside that raises ``IndexError`` (negative entries do not wrap as they do under
+        torch indexing on a CPU ring), a list whose length is not ``batch_size`` raises ``ValueError``; device tensors are passed
+        through unchecked, and the kernel leaves the samples of indices outside those bounds unwritten."""
+        if self.device.type != "cuda":
+            return self._sample_torch(batch_size, starts, envs)
+        t0, e = self._draw(batch_size, starts, envs)
+        given = starts is not None or envs is not None
+        # (the caller's own indices may name any row whose stacked frames lie inside the ring, as with torch indexing)
+        return _sample_fresh(_ring_layout(self, None), self.n_frames, batch_size, t0, e,
+                             self.capacity - self.n_frames if given else max(1, self.size - self.n_frames - 1))
 
     def __repr__(self):
         return f"Buffer(capacity={self.capacity}, obs_shape={self.obs_shape}, num_envs={self.num_envs})"
@@ -293,8 +421,97 @@ class TurnBuffer:
         """(states ``[capacity, E, C, V, V]``, actions, rewards, dones ``[capacity, E]``) of one agent slot: views."""
         return self.obs[:, :, a], self.actions[:, :, a], self.rewards[:, :, a], self.dones[:, :, a]
 
+    def sample(self, batch_size: int, agent=None, n_frames: int = 1, starts=None, envs=None):
+        """``Buffer.sample`` over the joint ring: states, actions (int64), rewards, next_states, dones, valid in the reference's
+        shapes.  ``agent=a`` samples (turn, env) pairs of that agent; ``agent=None`` samples over every (env, agent) pair, for learners
+        that share one model -- ``envs`` are then indices ``e * A + a``.  A CPU ring is read by torch indexing, a device ring by
+        one ``sgw_sample`` launch, where it lies (uint8 observations widen to float32 on the way).  Drawn starts lie in
+        ``[0, max(1, size - n_frames - 1))``; on a device ring given ones are checked as in ``Buffer.sample``:
+        ``0 <= start < capacity - n_frames``, ``0 <= env < E`` (``E * A`` with ``agent=None``), ``IndexError`` for a host list."""
+        E, A = self.num_envs, self.obs_shape[0]
+        cols = E * A if agent is None else E
+        hi = max(1, self.size - n_frames - 1)
+        given = starts is not None or envs is not None
+        t0 = torch.randint(0, hi, (batch_size,)) if starts is None else starts
+        e = torch.randint(0, cols, (batch_size,)) if envs is None else envs
+        if self.device.type == "cuda":
+            return _sample_fresh(_ring_layout(self, agent), n_frames, batch_size, t0, e, self.capacity - n_frames if given else hi)
+        if agent is None:
+            tail = self.obs_shape[1:]
+            st, ac = self.obs.reshape(self.capacity, cols, *tail), self.actions.reshape(self.capacity, cols)
+            rw, dn = self.rewards.reshape(self.capacity, cols), self.dones.reshape(self.capacity, cols)
+        else:
+            if not 0 <= int(agent) < A:
+                raise IndexError(f"agent {agent} outside [0, {A})")
+            st, ac, rw, dn = self.agent_view(int(agent))
+        s, a, r, ns, d, v = _stack_torch(st, ac, rw, dn, n_frames, batch_size, t0, e)
+        return s.to(torch.float32), a.to(torch.int64), r, ns.to(torch.float32), d, v
+
     def clear(self):
         self.idx = self.size = 0
 
     def __len__(self):
         return self.size
+
+
+class ReplaySampler:
+    """Training batches from a ``Buffer`` or a ``TurnBuffer`` on the device, one ``sgw_sample`` launch each, into storage this object
+    owns: ``sample()`` returns the reference's six-tuple (states, actions, rewards, next_states, dones, valid) as views of that
+    storage, valid until the next call.  With no indices given the kernel draws them itself from the counter RNG (stream
+    ``STREAM_SAMPLE``, keyed by ``seed`` and a device-side call counter): no allocation, no copy to or from the host, no
+    synchronisation, so a call can be recorded into a graph next to the turn and every replay draws a fresh batch.
+    ``last_index`` ``[B, 2]`` holds the (start, env) pairs the last call used.  ``agent`` as in ``TurnBuffer.sample``.
+    Given indices obey the bound of the draws, read from the ring at call time: ``0 <= start < max(1, size - n_frames - 1)``
+    (tighter than ``Buffer.sample``'s ``capacity - n_frames`` for given indices: a sampler only hands out rows the ring has
+    filled) and ``0 <= env <`` the ring's columns; host lists outside that raise ``IndexError``, a wrong length ``ValueError``,
+    device tensors are passed through unchecked (the kernel leaves such samples unwritten)."""
+
+    def __init__(self, ring, batch_size: int, *, n_frames=None, agent=None, seed: int = 0):
+        self.ring, self.batch_size, self.agent, self.seed = ring, int(batch_size), agent, int(seed)
+        self.n_frames = int(n_frames if n_frames is not None else getattr(ring, "n_frames", 1))
+        if self.batch_size < 1 or self.n_frames < 1:
+            raise ValueError("batch_size and n_frames must be at least 1")
+        layout = _ring_layout(ring, agent)
+        self.device = ring.device
+        s, ns, a, r, d, v = _sample_outputs(self.batch_size, self.n_frames, layout["R"], self.device)
+        for t in (s, ns, a, r, d, v):
+            t.zero_()
+        self._outs = (s, ns, a, r, d, v)
+        self.last_index = torch.zeros((self.batch_size, 2), dtype=torch.int64, device=self.device)
+        self.draw_count = torch.zeros((1,), dtype=torch.int64, device=self.device)     # (the kernel's uint64 counter)
+
+    def num_starts(self) -> int:
+        return max(1, self.ring.size - self.n_frames - 1)
+
+    def batch(self):
+        """The storage ``sample`` fills, in the order it returns it."""
+        s, ns, a, r, d, v = self._outs
+        return s, a, r, ns, d, v
+
+    def sample(self, starts=None, envs=None):
+        if (starts is None) != (envs is None):
+            raise ValueError("starts and envs are both given or both None")
+        layout = _ring_layout(self.ring, self.agent)
+        hi, B = self.num_starts(), self.batch_size
+        if starts is not None:
+            starts = _check_index_list("starts", starts, B, hi, self.device)
+            envs = _check_index_list("envs", envs, B, layout["cols"], self.device)
+        s, ns, a, r, d, v = self._outs
+        if self.device.type != "cuda":
+            if starts is None:
+                raise RuntimeError("ReplaySampler draws its indices on the device: a CPU ring needs starts and envs")
+            ring = self.ring
+            if isinstance(ring, TurnBuffer):
+                got = ring.sample(B, agent=self.agent, n_frames=self.n_frames, starts=starts, envs=envs)
+            else:
+                got = _stack_torch(ring.states, ring.actions, ring.rewards, ring.dones, self.n_frames, B, starts, envs)
+            for dst, src in zip((s, a, r, ns, d, v), got):
+                dst.copy_(src)
+            self.last_index.copy_(torch.from_numpy(np.stack([starts, envs], axis=1)))
+        else:
+            if starts is not None:
+                starts = torch.from_numpy(starts).to(self.device) if isinstance(starts, np.ndarray) else starts
+                envs = torch.from_numpy(envs).to(self.device) if isinstance(envs, np.ndarray) else envs
+            _launch_sample(layout, self.n_frames, B, self._outs, self.last_index, starts, envs, hi,
+                           count=self.draw_count if starts is None else None, seed=self.seed)
+        return self.batch()

@@ -69,6 +69,7 @@ namespace {
 #include "small_kernels.h"
 #include "resolve.h"
 #include "render.h"
+#include "sample.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -1237,6 +1238,67 @@ int sgw_render(const sgw_render_desc* d, void* stream) {
     if (vec4) { if (lds_atlas) launch_render<4, true>(p, blocks, lds, s); else launch_render<4, false>(p, blocks, lds, s); }
     else { if (lds_atlas) launch_render<1, true>(p, blocks, lds, s); else launch_render<1, false>(p, blocks, lds, s); }
     HIP_TRY(hipGetLastError());
+    return SGW_OK;
+}
+
+// ---------------------------------------------------------------- replay batches (sample.h)
+int sgw_sample(const sgw_sample_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_sample: desc is NULL");
+    if (!d->states || !d->actions || !d->rewards || !d->dones) return fail(SGW_EINVAL, "sgw_sample: states, actions, rewards and dones must not be NULL");
+    if (!d->out_states || !d->out_next_states || !d->out_actions || !d->out_rewards || !d->out_dones || !d->out_valid)
+        return fail(SGW_EINVAL, "sgw_sample: every output except out_index must not be NULL");
+    if (d->n < 0) return fail(SGW_EINVAL, "sgw_sample: n = %lld", (long long)d->n);
+    if (d->n_frames < 1) return fail(SGW_EINVAL, "sgw_sample: n_frames = %d", d->n_frames);
+    if (d->row_elems < 1 || d->row_elems >= (1ll << 30)) return fail(SGW_EINVAL, "sgw_sample: row_elems = %lld outside [1, 2^30)", (long long)d->row_elems);   // (the kernels index a row's units in 32 bits, a piece past its end included)
+    if (d->num_envs < 1 || d->num_envs >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_sample: num_envs = %lld outside [1, 2^31)", (long long)d->num_envs);
+    if (d->num_starts < 1 || d->num_starts >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_sample: num_starts = %lld outside [1, 2^31)", (long long)d->num_starts);
+    if (d->num_starts + d->n_frames > d->capacity)
+        return fail(SGW_EINVAL, "sgw_sample: num_starts + n_frames = %lld exceeds the capacity %lld: the last row read must lie inside the ring", (long long)(d->num_starts + d->n_frames), (long long)d->capacity);
+    if (!d->starts != !d->envs) return fail(SGW_EINVAL, "sgw_sample: starts and envs are both given or both NULL");
+    if (d->src_type != SGW_SAMPLE_F32 && d->src_type != SGW_SAMPLE_U8) return fail(SGW_EINVAL, "sgw_sample: unknown src_type %d", d->src_type);
+    if (d->act_type != SGW_SAMPLE_ACT_I64 && d->act_type != SGW_SAMPLE_ACT_U8) return fail(SGW_EINVAL, "sgw_sample: unknown act_type %d", d->act_type);
+    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    const bool u8 = d->src_type == SGW_SAMPLE_U8;
+    if (((u8 ? 0 : at(d->states)) | at(d->rewards) | at(d->dones) | at(d->out_states) | at(d->out_next_states) | at(d->out_rewards) | at(d->out_dones) | at(d->out_valid)) & 3)
+        return fail(SGW_EINVAL, "sgw_sample: misaligned float32 pointer");
+    if (((d->act_type == SGW_SAMPLE_ACT_I64 ? at(d->actions) : 0) | at(d->starts) | at(d->envs) | at(d->draw_count) | at(d->out_actions) | at(d->out_index)) & 7)
+        return fail(SGW_EINVAL, "sgw_sample: misaligned int64 pointer");
+    if (d->n > INT64_MAX / ((int64_t)d->n_frames + 1) / d->row_elems) return fail(SGW_EINVAL, "sgw_sample: n = %lld: the batch does not fit 64-bit offsets", (long long)d->n);
+    if (d->n == 0) return SGW_OK;
+    SampleParams p{};
+    p.states = d->states; p.actions = d->actions; p.rewards = d->rewards; p.dones = d->dones;
+    p.starts = d->starts; p.envs = d->envs; p.draw_count = d->draw_count;
+    p.out_states = d->out_states; p.out_next = d->out_next_states; p.out_actions = d->out_actions;
+    p.out_rewards = d->out_rewards; p.out_dones = d->out_dones; p.out_valid = d->out_valid; p.out_index = d->out_index;
+    p.n = d->n; p.num_envs = d->num_envs; p.num_starts = d->num_starts; p.R = d->row_elems;
+    p.sts = d->state_turn_stride; p.ses = d->state_env_stride; p.scs = d->scalar_turn_stride; p.sce = d->scalar_env_stride;
+    p.draw = d->draw; p.seed_lo = (uint32_t)d->seed; p.seed_hi = (uint32_t)(d->seed >> 32);
+    p.F = d->n_frames; p.act_u8 = d->act_type == SGW_SAMPLE_ACT_U8;
+    // 16 bytes per lane on the float32 side when every row -- source and destination -- starts on a 16-byte (uint8 source: 4-byte) boundary
+    const uintptr_t src_mask = u8 ? 3 : 15;
+    const int64_t src_elem = u8 ? 1 : 4;
+    const bool vec4 = (d->row_elems % 4) == 0 && !(at(d->states) & src_mask) && ((d->state_turn_stride * src_elem) & (int64_t)src_mask) == 0 &&
+                      ((d->state_env_stride * src_elem) & (int64_t)src_mask) == 0 && !((at(d->out_states) | at(d->out_next_states)) & 15);
+    const int per_piece = 64 * (vec4 ? 4 * (kSamplePieces / 2) : kSamplePieces);
+    p.pieces = (int)ceil_div(d->row_elems, (int64_t)per_piece);
+    const int64_t items = d->n * ((int64_t)d->n_frames + 1);
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(items, kBlock / 64), kSampleMaxBlocks);
+    const int64_t waves = (int64_t)blocks * (kBlock / 64);
+    p.step_k = waves / (d->n_frames + 1);
+    p.step_j = (int32_t)(waves % (d->n_frames + 1));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (vec4) {
+        if (u8) hipLaunchKernelGGL((sample_rows_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, s, p);
+        else hipLaunchKernelGGL((sample_rows_kernel<4, false>), dim3(blocks), dim3(kBlock), 0, s, p);
+    } else {
+        if (u8) hipLaunchKernelGGL((sample_rows_kernel<1, true>), dim3(blocks), dim3(kBlock), 0, s, p);
+        else hipLaunchKernelGGL((sample_rows_kernel<1, false>), dim3(blocks), dim3(kBlock), 0, s, p);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!d->starts && d->draw_count) {
+        hipLaunchKernelGGL(sample_count_kernel, dim3(1), dim3(64), 0, s, d->draw_count);
+        HIP_TRY(hipGetLastError());
+    }
     return SGW_OK;
 }
 
