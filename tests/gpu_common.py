@@ -14,7 +14,7 @@ from tests import helpers as H
 from tests.mixed_env import make_mixed_env, to_fixture_ids  # noqa: F401
 from tests.test_gpu_parity import assert_same  # noqa: F401
 
-__all__ = ['ROOT', 'torch_cuda', 'make_engine', '_tag_spec', '_cleanup_spec', 'KERNEL_CASES', 'make_env', '_run_bench', 'ROLLOUT_CASES', '_move_world', 'ROWS_CASES', 'PATCH_CASES', 'O_full', '_policy_env', '_long_horizon', '_values_and_expected', '_compare_turn', '_rollout_vs_oracle', '_float_world', 'SPEC_CASES', '_speculative_vs_oracle', '_LOOPS_SEEN', 'SWEEP_ROWS_CASES', 'N_ptr_array'] + ["assert_same", "make_mixed_env", "to_fixture_ids"]
+__all__ = ['ROOT', 'torch_cuda', 'make_engine', '_tag_spec', '_cleanup_spec', 'KERNEL_CASES', 'make_env', '_run_bench', 'ROLLOUT_CASES', '_move_world', 'ROWS_CASES', 'PATCH_CASES', 'O_full', '_policy_env', '_long_horizon', 'same_with_agent_state', '_values_and_expected', '_compare_turn', '_rollout_vs_oracle', '_float_world', 'SPEC_CASES', '_speculative_vs_oracle', '_LOOPS_SEEN', 'SWEEP_ROWS_CASES', 'N_ptr_array'] + ["assert_same", "make_mixed_env", "to_fixture_ids"]
 
 
 ROOT = H.ROOT
@@ -172,6 +172,16 @@ def _policy_env(E, shape=(13, 15, 5, 2), memory=6, seed=5):
     return make_env(h, w, a, r, E, p=0.05, seed=seed, model_factory=Policy)
 
 
+def same_with_agent_state(eng, co, ctx, what=("grid", "pos", "actions", "obs", "rewards", "total")):
+    """assert_same, and where the rule keeps them the agents' types (now and at observation time) and facings."""
+    assert_same(eng, co, what, ctx=ctx)
+    if eng.agent_state is not None:
+        assert np.array_equal(eng.agent_state.cpu().numpy(), co.agent_state), ctx + ": agent_state"
+        assert np.array_equal(eng.state_at_pov.cpu().numpy(), co.state_at_pov), ctx + ": state_at_pov"
+    if eng.agent_dir is not None:
+        assert np.array_equal(eng.agent_dir.cpu().numpy(), co.agent_dir), ctx + ": agent_dir"
+
+
 # ------------------------------------------------------------------ long horizons, one per kernel family
 def _long_horizon(torch, ws, E, T, check=(1, 2, 3, 10, 50, 100, 200, 350), first=3, epoch=1, expect=None, start=None):
     """T turns of random actions against the C oracle: every tensor (and the agents' types / facings where the rule keeps them) at
@@ -191,13 +201,7 @@ def _long_horizon(torch, ws, E, T, check=(1, 2, 3, 10, 50, 100, 200, 350), first
         if co is not None:
             co.grid[...], co.pos[...], co.total[...] = g0, p0, 0
 
-    def same(eng, co, ctx):
-        assert_same(eng, co, ctx=ctx)
-        if eng.agent_state is not None:
-            assert np.array_equal(eng.agent_state.cpu().numpy(), co.agent_state), ctx + ": agent_state"
-            assert np.array_equal(eng.state_at_pov.cpu().numpy(), co.state_at_pov), ctx + ": state_at_pov"
-        if eng.agent_dir is not None:
-            assert np.array_equal(eng.agent_dir.cpu().numpy(), co.agent_dir), ctx + ": agent_dir"
+    same = same_with_agent_state
 
     eng, co = make_engine(ws, E, first=first), H.COracle(ws, E, first_env_id=first)
     if expect:

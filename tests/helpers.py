@@ -251,3 +251,41 @@ def load_mixed(name="mixed_specs_treasurehunt"):
                                   [_MOVES.get(n, (0, 0))[0] for n in a["actions"]], [_MOVES.get(n, (0, 0))[1] for n in a["actions"]]))
         full.append(bool(a["full_view"]))
     return d, base, views, full, defs
+
+
+# ----------------------------------------------------------------------------- the kernel instances libsgw.so holds
+def canonical_instance(name: str, lanes: int):
+    """A plan's kernel name -> (template, full argument tuple) as `nm -C` spells the instance: trailing defaults filled in, the
+    SGW_AGENT_RULE_* macros and the packed kernels' `G` resolved, `(turn loop)` = the MULTI argument."""
+    import re
+
+    multi = name.endswith(" (turn loop)")
+    name = name.replace(" (turn loop)", "")
+    m = re.fullmatch(r"(\w+)<(.*)>", name)
+    assert m, name
+    tmpl, args = m.group(1), [a.strip() for a in m.group(2).split(",")]
+    rules = {"SGW_AGENT_RULE_MOVE": "0", "SGW_AGENT_RULE_TAG": "1", "SGW_AGENT_RULE_CLEANUP": "2", "SGW_MAX_AGENTS": str(__import__("sorrel_amd._native", fromlist=["x"]).MAX_AGENTS)}
+    args = [rules.get(a, str(lanes) if a == "G" else a) for a in args]
+    # (round 6: step_big has a ninth argument -- ROWS --, step_kernel a tenth -- the capacity of its per-agent LDS arrays -- and an eleventh -- ROWS)
+    defaults = {"step_fast": ["?"] * 6 + ["false"] * 6, "step_big": ["?"] * 4 + ["false", "false", "false", "512", "false"],
+                "step_kernel": ["?", "?", "0", "0", "0", "0", "0", "0", "false", "64", "false"],
+                "step_fast_rows": ["?"] * 5 + ["false", "false"]}.get(tmpl)      # (..., TAG, TAIL)
+    if defaults:
+        args += defaults[len(args):]
+        if multi:
+            args[{"step_kernel": 8, "step_big": 4}.get(tmpl, -1)] = "true"
+    return tmpl, tuple(args)
+
+
+def library_instances():
+    """Every kernel instance compiled into libsgw.so, as {(template, argument tuple)}, read from the host stubs `nm -C` lists."""
+    import re
+    import subprocess
+
+    out = subprocess.run(["nm", "-C", N.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    have = set()
+    for line in out.splitlines():
+        m = re.search(r"__device_stub__(\w+)<(.*)>\(", line.replace("(anonymous namespace)::", ""))
+        if m:
+            have.add((m.group(1), tuple(a.strip() for a in m.group(2).split(","))))
+    return have

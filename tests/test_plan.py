@@ -7,6 +7,8 @@ import sys
 
 import pytest
 
+from tests.helpers import canonical_instance as _canonical, library_instances
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
@@ -97,44 +99,13 @@ def test_a_specialised_instance_compiles_without_a_device(built, tmp_path):
         N.jit_compile("step_fast<true, 2, 6, 3, 32>")          # not an instance of the template: hipRTC's error comes back
 
 
-def _canonical(name: str, lanes: int):
-    """A plan's kernel name -> (template, full argument tuple) as `nm -C` spells the instance: trailing defaults filled in, the
-    SGW_AGENT_RULE_* macros and the packed kernels' `G` resolved, `(turn loop)` = the MULTI argument."""
-    import re
-
-    multi = name.endswith(" (turn loop)")
-    name = name.replace(" (turn loop)", "")
-    m = re.fullmatch(r"(\w+)<(.*)>", name)
-    assert m, name
-    tmpl, args = m.group(1), [a.strip() for a in m.group(2).split(",")]
-    rules = {"SGW_AGENT_RULE_MOVE": "0", "SGW_AGENT_RULE_TAG": "1", "SGW_AGENT_RULE_CLEANUP": "2", "SGW_MAX_AGENTS": str(__import__("sorrel_amd._native", fromlist=["x"]).MAX_AGENTS)}
-    args = [rules.get(a, str(lanes) if a == "G" else a) for a in args]
-    # (round 6: step_big has a ninth argument -- ROWS --, step_kernel a tenth -- the capacity of its per-agent LDS arrays -- and an eleventh -- ROWS)
-    defaults = {"step_fast": ["?"] * 6 + ["false"] * 6, "step_big": ["?"] * 4 + ["false", "false", "false", "512", "false"],
-                "step_kernel": ["?", "?", "0", "0", "0", "0", "0", "0", "false", "64", "false"]}.get(tmpl)
-    if defaults:
-        args += defaults[len(args):]
-        if multi:
-            args[{"step_kernel": 8, "step_big": 4}.get(tmpl, -1)] = "true"
-    return tmpl, tuple(args)
-
-
 def test_every_plan_without_specialised_instances_names_kernels_the_library_holds(built):
     """hipRTC absent (option jit = 0): whatever a plan of tools/plan_cases.py says will run -- whole turn, direct-store twin, rollout,
     walking variant, phase and row kernels -- is an instance compiled into libsgw.so (round 5 removed 26 turn-loop instances that
     spilled to scratch: nothing may still point at one)."""
-    import re
-    import subprocess
-
     import plan_cases
-    from sorrel_amd import _native as N
 
-    out = subprocess.run(["nm", "-C", N.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    have = set()
-    for line in out.splitlines():
-        m = re.search(r"__device_stub__(\w+)<(.*)>\(", line.replace("(anonymous namespace)::", ""))
-        if m:
-            have.add((m.group(1), tuple(a.strip() for a in m.group(2).split(","))))
+    have = library_instances()
     assert len(have) > 100
     checked = 0
     for case, plan in plan_cases.plans().items():
