@@ -336,6 +336,26 @@ int sgw_bind_agent_dir(sgw_engine* eng, uint8_t* agent_dir);
  * outside the grid.  Written by the lane that writes the reward; NULL unbinds (nothing is written, nothing is paid).  sgw_rollout has no
  * turn stride for it: the tensor holds the LAST turn of the call. */
 int sgw_bind_target_types(sgw_engine* eng, uint8_t* target_types);
+/* Encounter counts: what the agents stepped on, summed (GamblingAgent.encounters, sorrel/examples/iowa/agents.py:21-56;
+ * CleanupAgent.encounters, sorrel/examples/cleanup/agents.py:161-170).
+ * counts: device int64 [E][A][num_slots], caller-owned, 8-byte aligned; NULL unbinds (slot_of_type / num_slots are then ignored).
+ * slot_of_type: HOST array [cfg.num_types]; SGW_NO_SLOT = this type is not counted, else < num_slots.  num_slots in 1..32.
+ * Once bound, every call that makes an agent act -- sgw_step, every turn of an sgw_rollout launch, sgw_act / sgw_turn_act* -- counts:
+ *   SGW_AGENT_RULE_MOVE     an act whose action is valid and whose target lies inside the grid adds 1 to
+ *                           counts[env][a][slot_of_type[t]], t = the type on the agent layer of the target cell BEFORE the move (the
+ *                           value target_types records: an agent that takes a non-move action finds itself).
+ *   SGW_AGENT_RULE_CLEANUP  under the condition the reward has (valid action, target inside the grid): one increment PER LAYER, for
+ *                           the type that layer holds at the target cell, read where the reward is read -- after this act's beams are
+ *                           placed, before the move.  One act can add two or three to one slot; an agent that stays finds itself.
+ *   SGW_AGENT_RULE_TAG      refused (SGW_EINVAL): the reference keeps no such record there.
+ * An out-of-range entry of slot_of_type, num_slots outside 1..32 or a misaligned pointer give SGW_EINVAL before anything changes.
+ * The library never zeroes the counts: they run on across turns, across the turns of one sgw_rollout launch, across an auto-reset
+ * epoch boundary, across sgw_reset and across replays of a recorded graph; when to clear them is the caller's decision.  One writer
+ * per (env, agent) row and sequential acts within an env: plain read-modify-writes, no atomics.
+ * While counts are bound the engine does not advertise SGW_CAP_RESOLVE (a speculative pass replays acts and would count them more than
+ * once; drawn values set the precedent).  Unbinding restores exactly the kernels that ran before, as sgw_bind_target_types(NULL) does. */
+#define SGW_NO_SLOT 255
+int sgw_bind_encounters(sgw_engine* eng, int64_t* counts, const uint8_t* slot_of_type, int32_t num_slots);
 
 /* Observation element type written by sgw_step / sgw_observe.  SGW_OBS_F32 (default) is the contract
  * format (the reference's replay buffer stores float32, sorrel/buffers.py:31).  SGW_OBS_U8 is a

@@ -21,6 +21,7 @@ CAP_OBSERVE_ROWS, CAP_ACT, CAP_RESOLVE, CAP_OBS_AGENT_MAJOR, CAP_SWEEP_ROWS = 1,
 ACT_U8, ACT_I32, ACT_I64, ACT_QF32 = 0, 1, 2, 3
 STREAM_VALUE = 8            # which of its two values a type with a drawn value is worth (index = target cell)
 NO_TARGET = 255             # target_types: the agent's action was invalid or aimed outside the grid
+NO_SLOT = 255               # sgw_bind_encounters: a type that is not counted
 TAIL_NONE, TAIL_AGENT_IS_IT, TAIL_POSITION_TABLE = 0, 1, 2
 OK, EINVAL, EHIP, ENOMEM = 0, -1, -2, -3
 RENDER_COMPOSITE, RENDER_LAYERS = 0, 1
@@ -145,7 +146,7 @@ LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")
 # every symbol include/sgw.h declares
 EXPORTS = (
     "sgw_create", "sgw_destroy", "sgw_reset", "sgw_observe", "sgw_step", "sgw_rollout", "sgw_reduce_metrics",
-    "sgw_random_actions", "sgw_set_obs_format", "sgw_bind_agent_state", "sgw_init_agent_state", "sgw_bind_agent_dir", "sgw_bind_target_types", "sgw_get_status", "sgw_obs_elems_per_env", "sgw_grid_bytes_per_env",
+    "sgw_random_actions", "sgw_set_obs_format", "sgw_bind_agent_state", "sgw_init_agent_state", "sgw_bind_agent_dir", "sgw_bind_target_types", "sgw_bind_encounters", "sgw_get_status", "sgw_obs_elems_per_env", "sgw_grid_bytes_per_env",
     "sgw_algorithmic_bytes_per_env_step", "sgw_set_timing", "sgw_get_step_time_ms", "sgw_get_step_times_ms",
     "sgw_set_auto_reset", "sgw_set_wg_per_cu", "sgw_launch_info", "sgw_capabilities", "sgw_observe_rows", "sgw_act", "sgw_observe_full",
     "sgw_set_option", "sgw_plan", "sgw_jit_stats", "sgw_jit_compile", "sgw_bind_row_tail",
@@ -216,6 +217,8 @@ def load():
     lib.sgw_bind_agent_dir.restype = C.c_int
     lib.sgw_bind_target_types.argtypes = [vp, u8p]
     lib.sgw_bind_target_types.restype = C.c_int
+    lib.sgw_bind_encounters.argtypes = [vp, vp, vp, C.c_int32]
+    lib.sgw_bind_encounters.restype = C.c_int
     lib.sgw_init_agent_state.argtypes = [vp, u8p, vp]
     lib.sgw_init_agent_state.restype = C.c_int
     lib.sgw_get_status.argtypes = [vp, C.POINTER(C.c_int32), vp]

@@ -35,6 +35,8 @@ struct DevTables {
     // drawn values (sgw_config.type_value_alt / value_alt_prob): read from global memory by the acts of worlds that have one, never staged in LDS
     double value_alt[SGW_MAX_TYPES];
     uint64_t alt_thr[SGW_MAX_TYPES];                     // floor(p * 2^32); 2^32 = always, 0 = the type does not draw
+    // encounter counts (sgw_bind_encounters): the slot a type counts in (SGW_NO_SLOT: none); read from global memory by the acts of engines that bind counts
+    uint8_t enc_slot[SGW_MAX_TYPES];
 };
 constexpr int kTabFastBytes = offsetof(DevTables, appearance);
 constexpr int kTabAllBytes = offsetof(DevTables, value_alt);   // what the general (non one-hot) kernels copy into LDS
@@ -156,12 +158,15 @@ struct Params {
     uint32_t nturns;
     int64_t ts_obs, ts_act, ts_rew;
     // Drawn values and the record of what each agent stepped on (SGW_AGENT_RULE_MOVE).  `extras` is the one word the acts test, wave-uniformly,
-    // so that a world without either pays a scalar compare per act: bit 0 = some type draws its value, bit 1 = target_types is bound
+    // so that a world without either pays a scalar compare per act: bit 0 = some type draws its value, bit 1 = target_types is bound,
+    // bit 2 = encounter counts are bound (SGW_AGENT_RULE_MOVE and SGW_AGENT_RULE_CLEANUP)
     uint32_t extras;
     uint32_t drawn_mask;       // types with value_alt_prob > 0
     uint8_t* target_types;     // optional [E][A]: type id found on the target cell (255: invalid action / outside the grid)
+    int64_t* enc_counts;       // optional [E][A][enc_slots]: what every act found, summed (sgw_bind_encounters; the slot of a type: DevTables::enc_slot)
+    int enc_slots;
 };
-constexpr uint32_t kExtraDrawn = 1u, kExtraTargets = 2u;
+constexpr uint32_t kExtraDrawn = 1u, kExtraTargets = 2u, kExtraEncounters = 4u;
 // Who carries that code.  The instances the specialiser compiles for an engine have it compiled OUT (the uniform test cost the headline
 // 2 %: profiles/iowa_headline_ab.txt); an engine that draws values or keeps the record launches their `_x` twins (step_fast_x, step_big_x,
 // step_kernel_x, phase_rows_x: the same bodies with X = true), which exist in the specialiser's translation unit only.  The prebuilt instances
@@ -312,6 +317,15 @@ __device__ __forceinline__ uint32_t value_draw(const Params& p, const uint32_t c
 // ... and the value itself (Deck.draw: the base payoff, or base + loss): `otherwise` is type_value[t]
 __device__ __forceinline__ double drawn_value(const DevTables* gtab, const uint32_t t, const uint32_t u, const double otherwise) {
     return (uint64_t)u < gtab->alt_thr[t & 31u] ? gtab->value_alt[t & 31u] : otherwise;
+}
+
+// Encounter counts: one increment of row `row` (= env * A + agent) for the type `t` an act found.  There is ONE writer per row and the acts of
+// an env are sequential, so this is a plain read-modify-write: the thread that keeps the agent's records calls it, once per layer IN TURN (a
+// Cleanup act can find one slot on two or three layers -- several lanes adding to one address would lose increments).
+__device__ __forceinline__ void encounter_add(const Params& p, const int64_t row, const uint32_t t) {
+    if (t >= (uint32_t)p.T) return;
+    const uint32_t s = p.tab->enc_slot[t & 31u];
+    if (s < (uint32_t)p.enc_slots) p.enc_counts[row * p.enc_slots + s] += 1;
 }
 
 // RGBObservationSpec: np.clip(obs, 0, 255) / 255 on the float64 layer sum (observation_spec.py:483)

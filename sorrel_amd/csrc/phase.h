@@ -115,6 +115,7 @@ __global__ __launch_bounds__(kBlock, 8) void phase_kernel(const Params p) {
             }
             p.rewards[env * p.A + p.a0] = (float)val;
             if (p.target_types) p.target_types[env * p.A + p.a0] = (uint8_t)(tinb ? t : 255u);
+            if (p.enc_counts && tinb) encounter_add(p, env * p.A + p.a0, t);
             p.total[env] += val;                                               // float64, agent order (agent.py:172)
         }
     };
@@ -491,6 +492,7 @@ __device__ __forceinline__ int move_one(const Params& p, const DevTables* gtab, 
         }
         p.rewards[env * p.A + a] = (float)val;
         if (extras_of<XTRAS>(p) & kExtraTargets) p.target_types[env * p.A + a] = (uint8_t)(tinb ? t : 255u);
+        if ((extras_of<XTRAS>(p) & kExtraEncounters) && tinb) encounter_add(p, env * p.A + a, t);
         p.total[env] = tot + val;                                              // float64, agent order (agent.py:172)
         if (io.agent_action) p.actions[env * p.A + a] = (uint8_t)act;         // the record of what was taken
         if (io.reward_row) io.reward_row[env] = (float)val;
@@ -964,6 +966,8 @@ __global__ __launch_bounds__(kBlock, RULE == SGW_AGENT_RULE_CLEANUP ? 4 : 8) voi
                             col_new |= (uint64_t)tl[zl] << (8 * zl);
                         }
                     total_add = reward * (double)(p.total_factor - 1);       // the extra add inside act() (agents.py:172)
+                    if (writer && (p.extras & kExtraEncounters))             // what the act found, layer by layer: one thread, in turn (common.h)
+                        for (int zl = 0; zl < L; ++zl) encounter_add(p, env * p.A + a, tl[zl]);
                     uint32_t t = 0xFFu;
 #pragma unroll
                     for (int zl = 0; zl < SGW_MAX_LAYERS; ++zl)

@@ -492,6 +492,7 @@ __global__ __launch_bounds__(kBlock, 8) void turn_resolve(const Params p, const 
     if (live) {
         p.rewards[env * A + lane] = (float)val;
         if (p.target_types) p.target_types[env * A + lane] = (uint8_t)(ta != 0xFFFFFFFFu ? found : 255u);   // (engines with a drawn value do not advertise SGW_CAP_RESOLVE: this commit has no turn to draw for)
+        if (p.enc_counts && ta != 0xFFFFFFFFu) encounter_add(p, env * A + lane, found);   // (unreachable: engines with bound counts do not advertise SGW_CAP_RESOLVE either)
         if (passed) reinterpret_cast<uint16_t*>(p.pos)[env * A + lane] = (uint16_t)npos;
         if (ra.reward_rows) ra.reward_rows[(int64_t)lane * p.E + env] = (float)val;
         if (ra.action_rows) ra.action_rows[(int64_t)lane * p.E + env] = (int64_t)act;

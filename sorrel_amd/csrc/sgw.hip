@@ -775,6 +775,7 @@ int sgw_capabilities(sgw_engine* e) {
         bool ok = e->cfg.agent_rule == SGW_AGENT_RULE_MOVE && e->obs_format == SGW_OBS_F32 && e->cfg.num_agents <= 64;   // (the resolve kernel keeps an agent per lane)
         for (int a = 0; a < e->cfg.num_agents; ++a) ok = ok && !e->cfg.type_passable[e->cfg.agent_type[a]];
         ok = ok && !e->base.drawn_mask;   // (a drawn value: the commit of sgw_turn_resolve knows no turn -- such worlds take the sequential turn)
+        ok = ok && !e->base.enc_counts;   // (bound encounter counts: a speculative pass replays acts and would count them more than once)
         if (ok) caps |= SGW_CAP_RESOLVE;
     }
     if (e->big) caps |= SGW_CAP_OBS_AGENT_MAJOR;
@@ -1415,6 +1416,37 @@ int sgw_bind_target_types(sgw_engine* e, uint8_t* target_types) {
     // kept in the launch parameters every call starts from: every act sees it, and an unbound engine launches what it launched before
     e->base.target_types = target_types;
     e->base.extras = (e->base.extras & ~kExtraTargets) | (target_types ? kExtraTargets : 0u);
+    return SGW_OK;
+}
+
+int sgw_bind_encounters(sgw_engine* e, int64_t* counts, const uint8_t* slot_of_type, int32_t num_slots) {
+    if (!e) return fail(SGW_EINVAL, "sgw_bind_encounters: NULL engine");
+    if (!counts) {   // (an unbound engine launches what it launched before)
+        e->base.enc_counts = nullptr;
+        e->base.enc_slots = 0;
+        e->base.extras &= ~kExtraEncounters;
+        return SGW_OK;
+    }
+    if (e->cfg.agent_rule != SGW_AGENT_RULE_MOVE && e->cfg.agent_rule != SGW_AGENT_RULE_CLEANUP)
+        return fail(SGW_EINVAL, "sgw_bind_encounters: the counts are kept by the acts of SGW_AGENT_RULE_MOVE and SGW_AGENT_RULE_CLEANUP");
+    if (!slot_of_type) return fail(SGW_EINVAL, "sgw_bind_encounters: slot_of_type is NULL");
+    if (num_slots < 1 || num_slots > 32) return fail(SGW_EINVAL, "sgw_bind_encounters: num_slots must be in 1..32, not %d", (int)num_slots);
+    if (reinterpret_cast<uintptr_t>(counts) & 7u) return fail(SGW_EINVAL, "sgw_bind_encounters: counts must be 8-byte aligned");
+    uint8_t slots[SGW_MAX_TYPES];
+    memset(slots, SGW_NO_SLOT, sizeof(slots));
+    for (int t = 0; t < e->cfg.num_types; ++t) {
+        if (slot_of_type[t] != SGW_NO_SLOT && slot_of_type[t] >= num_slots)
+            return fail(SGW_EINVAL, "sgw_bind_encounters: slot_of_type[%d] = %d is neither SGW_NO_SLOT nor below num_slots = %d", t, (int)slot_of_type[t], (int)num_slots);
+        slots[t] = slot_of_type[t];
+    }
+    if (int rc = resolve_twins(e)) return rc;    // (compiled / loaded HERE, not inside a stream-ordered call)
+    // the slot table joins the engine's device tables (a blocking copy: binding is not stream-ordered); the rest is kept in the launch
+    // parameters every call starts from, like target_types
+    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(e->d_tab) + offsetof(DevTables, enc_slot), slots, sizeof(slots), hipMemcpyHostToDevice));
+    memcpy(e->h_tab.enc_slot, slots, sizeof(slots));
+    e->base.enc_counts = counts;
+    e->base.enc_slots = num_slots;
+    e->base.extras |= kExtraEncounters;
     return SGW_OK;
 }
 

@@ -425,6 +425,7 @@ __device__ __forceinline__ void step_big_body(const Params& p, [[maybe_unused]] 
                     val = drawn_value(gtab, jr & 31u, value_draw(p, cell, turn, env_id, ep4), val);
                 }
                 if (mine && (xtr & kExtraTargets)) p.target_types[env * p.A + tid] = (uint8_t)(validv ? (jr & 0xFFu) : 255u);
+                if (mine && validv && (xtr & kExtraEncounters)) encounter_add(p, env * p.A + tid, jr & 0xFFu);   // (lane = agent: every lane its own row)
             }
         }
         if constexpr (TAG) {

@@ -820,6 +820,16 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
                             val += __longlong_as_double(((long long)hi_ << 32) | lo_);
                         }
                         t = (uint32_t)__builtin_amdgcn_readfirstlane((int)lg[s_t]);
+                        if (extras_of<XTRAS>(p) & kExtraEncounters) {
+                            // encounter counts: lane s gathers what this act adds to slot s (a slot can be found on two or three layers), then
+                            // every lane with something to add does ONE read-modify-write of its own element -- no two lanes share an address
+                            uint32_t inc = 0;
+                            for (int zl = 0; zl < L; ++zl) {
+                                const uint32_t tz = (uint32_t)__builtin_amdgcn_readfirstlane((int)lg[zl * HW + tc]);
+                                if (tz < (uint32_t)p.T) inc += (uint32_t)gtab->enc_slot[tz & 31u] == (uint32_t)lane ? 1u : 0u;
+                            }
+                            if (inc && lane < p.enc_slots) p.enc_counts[(env * p.A + a) * p.enc_slots + lane] += inc;
+                        }
                     }
                     const bool pass = valid && t < (uint32_t)p.T && ((p.pass_mask >> (t & 31u)) & 1u);
                     if (pass && lane == 0) {
@@ -950,6 +960,8 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
             p.rewards[tix * p.ts_rew + env * p.A + lane] = __uint_as_float(rew_bits);
             if constexpr (!TAG)
                 if (extras_of<XTRAS>(p) & kExtraTargets) p.target_types[env * p.A + lane] = (uint8_t)xv;   // (a rollout's turns overwrite each other: the last one stays)
+            if constexpr (!TAG)   // (plain movers: a Cleanup act has added its layers already, and its xv is not a type)
+                if ((extras_of<XTRAS>(p) & kExtraEncounters) && (!RULES || p.agent_rule == SGW_AGENT_RULE_MOVE) && xv != 255u) encounter_add(p, env * p.A + lane, xv);   // (... and these add up: lane = agent, every lane its own row)
             if (p.state_at_pov) p.state_at_pov[env * p.A + lane] = (uint8_t)pov_type;
         }
         if (tix + 1 < nturns) yx = moved ? npos : yx;   // the next turn starts where this one ended

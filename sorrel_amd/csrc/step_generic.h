@@ -268,6 +268,8 @@ __device__ __forceinline__ void step_kernel_body(const Params& p, [[maybe_unused
                     if (inb) {
                         for (int zl = 0; zl < p.L; ++zl) val += tab->value[lg[zl * HW + ny * W + nx] & 31u];   // all layers, BEFORE the move
                         t = lg[zoff + ny * W + nx];
+                        if (gtid == 0 && (extras_of<XTRAS>(p) & kExtraEncounters))    // what the act found, layer by layer: one thread, in turn (common.h)
+                            for (int zl = 0; zl < p.L; ++zl) encounter_add(p, env * p.A + a, lg[zl * HW + ny * W + nx]);
                     }
                     const bool pass = inb && t < (uint32_t)p.T && ((p.pass_mask >> (t & 31u)) & 1u);
                     gsync<WPE>();
@@ -311,6 +313,7 @@ __device__ __forceinline__ void step_kernel_body(const Params& p, [[maybe_unused
                         if ((xtr & kExtraDrawn) && inb && tok && ((p.drawn_mask >> (t & 31u)) & 1u))
                             val = drawn_value(p.tab, t, value_draw(p, (uint32_t)taddr, turn, env_id, ep4), val);
                         if (gtid == 0 && (xtr & kExtraTargets)) p.target_types[env * p.A + a] = (uint8_t)(inb ? t : 255u);
+                        if (gtid == 0 && inb && (xtr & kExtraEncounters)) encounter_add(p, env * p.A + a, t);
                     }
                 }
                 const bool pass = inb && tok && ((p.pass_mask >> (t & 31u)) & 1u);
@@ -582,6 +585,8 @@ __device__ __forceinline__ void step_kernel_body(const Params& p, [[maybe_unused
                     if (inb) {
                         for (int zl = 0; zl < p.L; ++zl) val += tab->value[lg[zl * HW + ny * W + nx] & 31u];   // all layers, BEFORE the move
                         t = lg[zoff + ny * W + nx];
+                        if (atid == 0 && (extras_of<XTRAS>(p) & kExtraEncounters))    // what the act found, layer by layer: one thread, in turn (common.h)
+                            for (int zl = 0; zl < p.L; ++zl) encounter_add(p, env * p.A + a, lg[zl * HW + ny * W + nx]);
                     }
                     const bool pass = inb && t < (uint32_t)p.T && ((p.pass_mask >> (t & 31u)) & 1u);
                     gsync<WPA>();
@@ -618,6 +623,7 @@ __device__ __forceinline__ void step_kernel_body(const Params& p, [[maybe_unused
                         if ((xtr & kExtraDrawn) && inb && tok && ((p.drawn_mask >> (t & 31u)) & 1u))
                             val = drawn_value(p.tab, t, value_draw(p, (uint32_t)taddr, turn, env_id, ep4), val);
                         if (atid == 0 && (xtr & kExtraTargets)) p.target_types[env * p.A + a] = (uint8_t)(inb ? t : 255u);
+                        if (atid == 0 && inb && (xtr & kExtraEncounters)) encounter_add(p, env * p.A + a, t);
                     }
                 }
                 const bool pass = inb && tok && ((p.pass_mask >> (t & 31u)) & 1u);

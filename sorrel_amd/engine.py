@@ -132,6 +132,10 @@ class GridEngine:
         self.target_types = None
         if tensors.get("target_types") is not None:
             self.bind_target_types(tensors["target_types"])
+        # what the agents found, summed (int64 [E, A, K]): on request only -- (slot_of_type, K, counts)
+        self.encounters = None
+        if tensors.get("encounters") is not None:
+            self.bind_encounters(*tensors["encounters"])
 
     def bind_target_types(self, t=True):
         """``sgw_bind_target_types``: from now on every act of a plain mover records the entity type it found on its target cell in
@@ -149,6 +153,37 @@ class GridEngine:
         N.check(self._lib.sgw_bind_target_types(self._h, self._ptr(t)))
         self.target_types = t
         return t
+
+    def bind_encounters(self, slot_of_type, num_slots=None, counts=None):
+        """``sgw_bind_encounters``: from now on every act of a plain mover or a Cleanup agent adds what it found on its target cell to
+        ``self.encounters`` (int64 ``[E, A, num_slots]``): plain movers the type on the agent layer, Cleanup agents the type on every layer.
+        ``slot_of_type``: one entry per entity type of the spec, the slot the type counts in or ``N.NO_SLOT``; None unbinds.  ``counts``
+        adopts a tensor (it is not zeroed: the library never clears the counts, the caller decides when), default a zeroed one.
+        ``ValueError`` for what the library refuses: Tag agents, a slot outside ``[0, num_slots)``, ``num_slots`` outside 1..32."""
+        if slot_of_type is None:
+            N.check(self._lib.sgw_bind_encounters(self._h, None, None, 0))
+            self.encounters = None
+            return None
+        E, A, T = self.num_envs, self.spec.num_agents, int(self.config.num_types)
+        slots = [int(s) for s in slot_of_type]
+        if len(slots) != T:
+            raise ValueError(f"slot_of_type needs one entry per entity type: {T}, not {len(slots)}")
+        if any(s < 0 or s > 255 for s in slots):
+            raise ValueError("slot_of_type entries are slot numbers or N.NO_SLOT (255)")
+        if num_slots is None:
+            num_slots = max([s + 1 for s in slots if s != N.NO_SLOT], default=0)
+        K = int(num_slots)
+        if not 1 <= K <= 32:
+            raise ValueError(f"num_slots must be in 1..32, not {K}")
+        if counts is None:
+            counts = torch.zeros((E, A, K), dtype=torch.int64, device=self.device)
+        if tuple(counts.shape) != (E, A, K) or counts.dtype != torch.int64 or counts.device != self.device or not counts.is_contiguous():
+            raise ValueError(f"counts must be contiguous int64 [{E}, {A}, {K}] on the engine's device")
+        table = (C.c_uint8 * T)(*slots)
+        with self._on_device():
+            N.check(self._lib.sgw_bind_encounters(self._h, self._ptr(counts), C.cast(table, C.c_void_p), K))
+        self.encounters = counts
+        return counts
 
     # ------------------------------------------------------------------ util
     def _stream(self):

@@ -327,6 +327,9 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
             if tt is None or tuple(tt.shape) != (w.num_envs, len(self.agents)):
                 tt = torch.full((w.num_envs, len(self.agents)), 255, dtype=torch.uint8, device=w.device)
             w.target_types = tensors["target_types"] = tt
+        if self.record_encounters:                            # what every agent found, summed (sgw_bind_encounters): one tensor, every handle
+            kinds, slots = self._encounter_slots()
+            tensors["encounters"] = (slots, len(kinds), self._encounter_tensor(kinds))
         # agents that differ, or whose own spec is the whole map, step one after another on their own handles (take_turn); no handle
         # then needs the [E][A][C][V][V] tensor of a fused turn
         self._mixed = len(distinct) > 1 or any(a.observation_spec.full_view for a in self.agents)
@@ -401,6 +404,67 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
     def target_types(self):
         self._ensure_engine()
         return getattr(self.world, "target_types", None)
+
+    #: keep ``env.encounters`` (int64 ``[E, A, K]``): how often every agent found each kind of entity on the cell it acted on -- plain movers
+    #: the agent layer of the target (``GamblingAgent.encounters``), Cleanup agents every layer of it (``CleanupAgent.encounters``); counted by
+    #: the acts themselves (``sgw_bind_encounters``), so a fused rollout counts like a loop of turns.  True: one slot per distinct ``kind`` of the
+    #: type registry, in registration order (types that share a kind share the slot); a sequence of kind names: exactly those slots, in that
+    #: order, every other kind uncounted.  Never cleared by the engine or by ``reset()``: ``clear_encounters()`` is the caller's decision.
+    #: Not for Tag agents.  With counts kept the engine offers no ``sgw_turn_resolve`` (its passes replay acts): ``speculate_turns`` plays the generic
+    #: speculative turn, which treats the counts as state -- every pass starts from the turn's counts on the scratch handle, the last pass's are kept.
+    record_encounters = False
+
+    def _encounter_slots(self):
+        """``(kinds, slot_of_type)`` of the registry as it stands: the slot names, and for every entity type its slot (``N.NO_SLOT``: not counted)."""
+        from sorrel_amd import _native as N
+
+        protos = self.world.registry.prototypes
+        if self.record_encounters is True:
+            kinds = tuple(dict.fromkeys(p.kind for p in protos))
+        else:
+            kinds = tuple(self.record_encounters)
+            if len(set(kinds)) != len(kinds):
+                raise ValueError("record_encounters names a kind twice")
+        if not 1 <= len(kinds) <= 32:
+            raise ValueError(f"record_encounters: 1..32 kinds can be counted, not {len(kinds)}")
+        index = {k: i for i, k in enumerate(kinds)}
+        return kinds, [index.get(p.kind, N.NO_SLOT) for p in protos]
+
+    def _encounter_tensor(self, kinds):
+        """The one int64 ``[E, A, K]`` tensor every handle binds; it lives on the world and survives engine rebuilds (a kind that appears
+        later -- ``record_encounters = True`` and a type registered after the first turn -- gets a new column, the others keep their counts)."""
+        w = self.world
+        old, old_kinds = getattr(w, "encounters", None), getattr(w, "encounter_kinds", ())
+        shape = (w.num_envs, len(self.agents), len(kinds))
+        if old is None or tuple(old_kinds) != tuple(kinds) or tuple(old.shape) != shape:
+            new = torch.zeros(shape, dtype=torch.int64, device=w.device)
+            if old is not None and tuple(old.shape[:2]) == shape[:2]:
+                for i, k in enumerate(kinds):
+                    if k in old_kinds:
+                        new[:, :, i] = old[:, :, old_kinds.index(k)]
+            w.encounters, w.encounter_kinds = new, tuple(kinds)
+        return w.encounters
+
+    @property
+    def encounter_kinds(self):
+        """The names of the slots of ``encounters``, in order (None: nothing is recorded)."""
+        if not self.record_encounters:
+            return None
+        if self.record_encounters is True:
+            self._ensure_engine()          # (compiling the specs may register types: the slots are those of the tables the engine runs)
+        return self._encounter_slots()[0]
+
+    @property
+    def encounters(self):
+        """int64 ``[E, A, K]`` in ``encounter_kinds`` order: the tensor the engine's acts add to (None: nothing is recorded)."""
+        kinds = self.encounter_kinds
+        return None if kinds is None else self._encounter_tensor(kinds)
+
+    def clear_encounters(self) -> None:
+        """Zero the counts (stream-ordered; the tensor stays where it is, so a recorded turn keeps counting into it)."""
+        enc = self.encounters
+        if enc is not None:
+            enc.zero_()
 
     def _keep_turn_state(self, eng) -> None:
         """The device's turn state at the turn in flight: ``sgw_act`` has no turn argument and keys what it draws -- exploration, drawn

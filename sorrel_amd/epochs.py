@@ -254,7 +254,7 @@ class EpochLoops:
     # "# TODO: ability to save/load?" at sorrel/environment.py:107)
     def state_dict(self) -> dict:
         """Everything a rollout needs to continue bit-exactly: the grid, agent positions, ``total_reward``, the
-        per-agent state / facing tensors, the epoch / turn counters, the RNG seed and the first global env id."""
+        per-agent state / facing tensors, the encounter counts where they are recorded, the epoch / turn counters, the RNG seed and the first global env id."""
         w = self.world
         eng = self._ensure_engine()
         sd = dict(version=1, grid=w.grid.cpu().clone(), agent_pos=w.agent_pos.cpu().clone(),
@@ -266,6 +266,9 @@ class EpochLoops:
             sd["agent_state"] = eng.agent_state.cpu().clone()
         if eng.agent_dir is not None:
             sd["agent_dir"] = eng.agent_dir.cpu().clone()
+        if self.record_encounters:
+            sd["encounters"] = self.encounters.cpu().clone()
+            sd["encounter_kinds"] = list(self.encounter_kinds)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -277,6 +280,8 @@ class EpochLoops:
             raise ValueError("checkpoint was taken with another seed / first global env id: the rollout would not continue bit-exactly")
         if list(sd["type_names"]) != [type(p).__name__ for p in w.registry.prototypes]:
             raise ValueError("checkpoint was taken with another entity type table")
+        if self.record_encounters and ("encounters" not in sd or list(sd["encounter_kinds"]) != list(self.encounter_kinds)):
+            raise ValueError("this environment records encounters: the checkpoint must carry the counts of the same kinds")
         w.grid.copy_(sd["grid"].to(w.device))
         w.agent_pos.copy_(sd["agent_pos"].to(w.device))
         w.total_reward.copy_(sd["total_reward"].to(w.device))
@@ -284,6 +289,8 @@ class EpochLoops:
             eng.agent_state.copy_(sd["agent_state"].to(w.device))
         if "agent_dir" in sd and eng.agent_dir is not None:
             eng.agent_dir.copy_(sd["agent_dir"].to(w.device))
+        if self.record_encounters:
+            self.encounters.copy_(sd["encounters"].to(w.device))
         self.epoch, self.turn = int(sd["epoch"]), int(sd["turn"])
         eng.epoch, eng.turn = self.epoch, self.turn
         w.is_done = bool(sd.get("is_done", False))

@@ -56,7 +56,19 @@ class CleanupAgent(MovingAgent):
     def __init__(self, observation_spec, action_spec, model, beam_radius: int = 3):
         super().__init__(observation_spec, action_spec, model)
         self.interaction_rule = CleanupRule(beam_radius, CleanBeam, ZapBeam)
-        self.encounters = {}
+
+    @property
+    def encounters(self) -> torch.Tensor:
+        """How often this agent found each kind of entity on the cell it acted on, every layer of it, per env: int64 ``[E, K]`` in
+        ``env.encounter_kinds`` order (the reference's dict, ``agents.py:161-170``, for every env of the batch).  Counted by the engine's
+        acts (``Environment.record_encounters``); never cleared by ``reset()``, as in the reference."""
+        return self._world._environment.encounters[:, self.slot]
+
+    def encounter_dict(self, env: int = 0) -> dict:
+        """The reference's ``{kind: n}`` for one env (synchronising).  A kind appears once it has been found: the reference adds keys
+        on first encounter, so a zero count is absent."""
+        kinds = self._world._environment.encounter_kinds
+        return {k: int(n) for k, n in zip(kinds, self.encounters[env].tolist()) if n}
 
     @property
     def directions(self) -> torch.Tensor:

@@ -58,7 +58,9 @@ class Apple(Entity):
 class AppleTree(Entity):
     """Grows an apple with probability ``world.apple_spawn_chance`` per turn; the pollution gate
     (``world.pollution > world.pollution_threshold``) reads an attribute the reference never
-    updates, so it is evaluated once at compile time (entities.py:76-90)."""
+    updates, so it is evaluated once at compile time (entities.py:76-90).  The apple takes the tree's place (same cell,
+    same layer) and the tree comes back when it is eaten: an agent that acts on the cell counts one of the two, ``AppleTree`` or ``Apple``,
+    in ``CleanupAgent.encounters`` -- "apples eaten" is the ``Apple`` slot."""
 
     transition_rule = SpawnRule(
         lambda world: 0.0 if world.pollution > world.pollution_threshold else world.apple_spawn_chance,

@@ -15,6 +15,8 @@ class CleanupEnv(Environment):
     """config keys as in ``sorrel/examples/cleanup/configs``: ``env.*``, ``agent.agent.num``,
     ``agent.agent.beam_radius``, ``agent.agent.obs.vision`` / ``.embeddings``."""
 
+    record_encounters = True     # CleanupAgent.encounters: every kind of the registry, counted by the engine's acts
+
     def __init__(self, world, config, model_factory=None):
         self._model_factory = model_factory
         super().__init__(world, config)

@@ -14,8 +14,8 @@ class GamblingAgent(MovingAgent):
     @property
     def encounters(self) -> torch.Tensor:
         """How often this agent stepped on each deck this epoch, per env: int64 ``[E, 4]`` in ``DECK_KINDS`` order (the
-        reference's dict, ``agents.py:22``, for every env of the batch).  Kept by the environment from the engine's record of what
-        every agent found on its target cell (``Environment.record_targets``)."""
+        reference's dict, ``agents.py:22``, for every env of the batch).  Counted by the engine's acts into the environment's tensor
+        (``Environment.record_encounters``); ``reset()`` clears it, as the reference's does."""
         return self._world._environment.encounters[:, self.slot]
 
     def encounter_counts(self) -> dict:

@@ -1,6 +1,4 @@
 """``GamblingEnv`` (``sorrel/examples/iowa/env.py:28-224``) on the batched engine."""
-import torch
-
 from sorrel_amd.action.action_spec import ActionSpec
 from sorrel_amd.environment import Environment
 from sorrel_amd.examples.iowa.agents import GamblingAgent
@@ -14,11 +12,11 @@ ENTITY_LIST = ["EmptyEntity", "Wall", "Sand", "DeckA", "DeckB", "DeckC", "DeckD"
 class GamblingEnv(Environment):
     """config keys: ``world.{height,width,spawn_prob}``, ``model.agent_vision_radius``, optional ``model.num_agents`` (default 2)."""
 
-    record_targets = True        # the engine records what every agent stepped on: the encounters are counted from it
+    record_targets = True        # the engine records what every agent stepped on in the last turn (``env.target_types``)
+    record_encounters = tuple(DECK_KINDS)    # ... and counts the decks among it: ``env.encounters``, int64 [E, A, 4], added to by the acts themselves
 
     def __init__(self, world, config, model_factory=None):
         self._model_factory = model_factory
-        self._fold = None
         super().__init__(world, config)
 
     def setup_agents(self):
@@ -37,7 +35,6 @@ class GamblingEnv(Environment):
                 model = RandomModel(ospec.input_size, aspec.n_actions)
             agents.append(GamblingAgent(ospec, aspec, model))
         self.agents = agents
-        self.encounters = torch.zeros((self.world.num_envs, n, len(DECK_KINDS)), dtype=torch.int64, device=self.world.device)
 
     def populate_environment(self):
         """Walls around BOTH layers, sand below, spawning EmptyEntity on the top layer, agents on distinct random interior
@@ -46,25 +43,8 @@ class GamblingEnv(Environment):
         self.spawn_agents()
 
     # ------------------------------------------------------------------ encounters
-    def _fold_table(self) -> torch.Tensor:
-        """int64 ``[256, 4]``: row t is the one-hot of the deck kind of entity type t (fresh and drawn twins fold onto their kind),
-        zero for everything else and for 255 (no target)."""
-        reg = self.world.registry
-        if self._fold is None or self._fold[0] != reg.version:
-            table = torch.zeros((256, len(DECK_KINDS)), dtype=torch.int64)
-            for t, proto in enumerate(reg.prototypes):
-                if proto.kind in DECK_KINDS:
-                    table[t, DECK_KINDS.index(proto.kind)] = 1
-            self._fold = (reg.version, table.to(self.world.device))
-        return self._fold[1]
-
-    def _end_of_turn(self, eng) -> None:
-        # GamblingAgent.act's bookkeeping (agents.py:54-56) for every env and agent at once, from the turn's record; recorded with the turn
-        self.encounters += self._fold_table()[eng.target_types.long()]
-
-    def rollout(self, turns: int) -> None:
-        for _ in range(int(turns)):          # (the record holds one turn: the encounters are counted turn by turn)
-            self.take_turn()
+    # GamblingAgent.act's bookkeeping (agents.py:54-56) is done by the engine's acts (sgw_bind_encounters): fresh and drawn deck twins share
+    # their kind's slot, everything else is uncounted.  Nothing is folded on the host, so rollout() is Environment.rollout: one launch.
 
     def run_experiment(self, animate: bool = False, logging: bool = True, logger=None, output_dir=None, epochs=None, max_turns=None,
                        all_reduce: bool = True):

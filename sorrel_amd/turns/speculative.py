@@ -128,6 +128,9 @@ class SpeculativeTurns:
             t["agent_dir"] = eng.agent_dir.clone()
         if eng.target_types is not None:
             t["target_types"] = torch.full_like(eng.target_types, 255)
+        if eng.encounters is not None:        # counts are state: every pass starts from the turn's counts, the last pass's are the turn's (a scratch tensor of its own)
+            kinds, slots = self._encounter_slots()
+            t["encounters"] = (slots, len(kinds), torch.zeros_like(eng.encounters))
         played = GridEngine(eng.spec, eng.num_envs, device=eng.device, first_env_id=eng.first_env_id, tensors=t, obs_dtype=eng.obs_dtype)
         self.__dict__["_spec_scratch"] = (eng, played)
         self._aux_engines[("speculation scratch", eng.uid)] = played      # (raise_on_status polls it; closed with the others)
@@ -174,6 +177,8 @@ class SpeculativeTurns:
             state.append(("agent_state", eng.agent_state, played.agent_state))
         if eng.agent_dir is not None:
             state.append(("agent_dir", eng.agent_dir, played.agent_dir))
+        if eng.encounters is not None:                                   # (a pass replays acts: each starts from the counts the turn began with)
+            state.append(("encounters", eng.encounters, played.encounters))
         k = 0
         while True:
             k += 1
