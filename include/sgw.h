@@ -666,6 +666,43 @@ typedef struct sgw_sample_desc {
 /* Asynchronous on `stream`.  Bad arguments: SGW_EINVAL with the reason in sgw_last_error(), before anything is launched. */
 int sgw_sample(const sgw_sample_desc* desc, void* stream);
 
+/* ---- discounted returns (sorrel/models/pytorch/ppo.py:226-239: the head of PyTorchPPO.train_step, for every column of a ring) ----
+ * One launch walks `count` ring rows backwards in time, a lane per column: with row(t) = (first + t) mod capacity, t = count-1 .. 0,
+ *     d = 0 where dones[row(t)][c] != 0;   d = fl32(rewards[row(t)][c] + fl32((float)gamma * d));   out_returns[t][c] = d
+ * -- float32 with the product and the sum rounded separately (no fused multiply-add): the reference's arithmetic, bit for bit.
+ * Element (row, c) of rewards and of dones lies at row * turn_stride + c * col_stride, so a Buffer ([capacity][E]: strides E / 1),
+ * every agent of a TurnBuffer ([capacity][E][A]: cols = E * A, strides E * A / 1) and one agent of it (pointers offset by a, cols = E,
+ * strides E * A / A) are read where they lie.  out_returns is [count][cols], contiguous; row 0 is ring row `first`.
+ * normalize: (x - mean) / (std + 1e-7) in float64 with the unbiased std, written to out_normalized ([count][cols], out_type):
+ *   SGW_RETURNS_NORM_COLUMN  mean / std of each column's count values (the reference's normalisation, per world and agent), same launch
+ *   SGW_RETURNS_NORM_ALL     one mean / std over all count * cols values: per-workgroup partial moments in `workspace`
+ *                            (sgw_returns_workspace_bytes), merged in a fixed order by a second launch; results are reproducible
+ * The float32 out_type is the float64 value rounded once.  One value (count == 1, or count * cols == 1) gives NaN, as the reference.
+ * out_stats (or NULL) receives (mean, std) pairs: [cols][2] for NORM_COLUMN, [2] for NORM_ALL.  count == 0 launches nothing.
+ * Needs no engine; all pointers are device pointers.  Asynchronous on `stream`; bad arguments: SGW_EINVAL with the reason in
+ * sgw_last_error(), before anything is launched. */
+#define SGW_RETURNS_NORM_NONE 0
+#define SGW_RETURNS_NORM_COLUMN 1
+#define SGW_RETURNS_NORM_ALL 2
+#define SGW_RETURNS_OUT_F64 0    /* out_type: out_normalized is float64 */
+#define SGW_RETURNS_OUT_F32 1    /* ... float32 */
+typedef struct sgw_returns_desc {
+    const float* rewards;
+    const float* dones;          /* any non-zero value ends an episode */
+    float* out_returns;          /* [count][cols] */
+    void* out_normalized;        /* [count][cols] of out_type; NULL with SGW_RETURNS_NORM_NONE */
+    double* out_stats;           /* (mean, std) pairs, or NULL */
+    void* workspace;             /* SGW_RETURNS_NORM_ALL: sgw_returns_workspace_bytes(count, cols) bytes, 8-byte aligned */
+    int64_t workspace_bytes;
+    int64_t first, count, capacity, cols;     /* 0 <= first < capacity; 0 <= count <= capacity; 1 <= cols < 2^31 */
+    int64_t turn_stride, col_stride;          /* in elements, >= 1: rewards and dones share them */
+    double gamma;                /* rounded to float32 by a C cast */
+    int32_t normalize, out_type, reserved0, reserved1;        /* reserved: 0 */
+} sgw_returns_desc;
+int sgw_returns(const sgw_returns_desc* desc, void* stream);
+/* Bytes of workspace SGW_RETURNS_NORM_ALL needs for this shape (0 for no turns); a negative code for a shape sgw_returns rejects. */
+int64_t sgw_returns_workspace_bytes(int64_t count, int64_t cols);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

@@ -29,6 +29,8 @@ TILE_OPAQUE, TILE_CLEAR, TILE_KEEP = 1, 2, 0xFFFF
 STREAM_SAMPLE = 9           # sgw_sample's drawn (start, env) pairs: epoch 0, turn / env slots = low / high word of the draw counter
 SAMPLE_F32, SAMPLE_U8 = 0, 1
 SAMPLE_ACT_I64, SAMPLE_ACT_U8 = 0, 1
+RETURNS_NORM_NONE, RETURNS_NORM_COLUMN, RETURNS_NORM_ALL = 0, 1, 2
+RETURNS_OUT_F64, RETURNS_OUT_F32 = 0, 1
 
 
 class SgwConfig(C.Structure):
@@ -140,6 +142,20 @@ class SgwSampleDesc(C.Structure):
     ]
 
 
+class SgwReturnsDesc(C.Structure):
+    """Mirror of ``struct sgw_returns_desc`` (include/sgw.h): one ``sgw_returns`` call."""
+
+    _fields_ = [
+        ("rewards", C.c_void_p), ("dones", C.c_void_p), ("out_returns", C.c_void_p), ("out_normalized", C.c_void_p),
+        ("out_stats", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("first", C.c_int64), ("count", C.c_int64), ("capacity", C.c_int64), ("cols", C.c_int64),
+        ("turn_stride", C.c_int64), ("col_stride", C.c_int64),
+        ("gamma", C.c_double),
+        ("normalize", C.c_int32), ("out_type", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -151,6 +167,7 @@ EXPORTS = (
     "sgw_set_auto_reset", "sgw_set_wg_per_cu", "sgw_launch_info", "sgw_capabilities", "sgw_observe_rows", "sgw_act", "sgw_observe_full",
     "sgw_set_option", "sgw_plan", "sgw_jit_stats", "sgw_jit_compile", "sgw_bind_row_tail",
     "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render", "sgw_sample",
+    "sgw_returns", "sgw_returns_workspace_bytes",
     "sgw_last_error", "sgw_version",
 )
 
@@ -292,6 +309,10 @@ def load():
     lib.sgw_render.restype = C.c_int
     lib.sgw_sample.argtypes = [C.POINTER(SgwSampleDesc), vp]
     lib.sgw_sample.restype = C.c_int
+    lib.sgw_returns.argtypes = [C.POINTER(SgwReturnsDesc), vp]
+    lib.sgw_returns.restype = C.c_int
+    lib.sgw_returns_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.sgw_returns_workspace_bytes.restype = C.c_int64
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

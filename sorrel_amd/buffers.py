@@ -132,6 +132,128 @@ def _sample_fresh(layout, n_frames, batch_size, t0, e, num_starts):
     return s, a, r, ns, dn, v
 
 
+class Returns:
+    """What ``Buffer.returns`` / ``TurnBuffer.returns`` give back: ``returns`` float32 ``[count, E]`` (``[count, E, A]`` over every agent
+    of a ``TurnBuffer``), row 0 the oldest turn of the segment; ``normalized`` of the asked dtype and ``mean`` / ``std`` (float64: one
+    value per column for ``normalize="column"``, 0-d tensors for ``"all"``) or None without normalisation.  Passed back as ``out=``
+    its tensors are overwritten in place."""
+
+    __slots__ = ("returns", "normalized", "mean", "std", "_stats", "_workspace", "_mode")
+
+    def __init__(self, shape, normalize, dtype, device):
+        from sorrel_amd import _native as N
+
+        cols = int(np.prod(shape[1:]))
+        self._mode = normalize
+        self.returns = torch.empty(shape, dtype=torch.float32, device=device)
+        self.normalized = self.mean = self.std = self._stats = self._workspace = None
+        if normalize is not None:
+            self.normalized = torch.empty(shape, dtype=dtype, device=device)
+            self._stats = torch.empty((cols, 2) if normalize == "column" else (2,), dtype=torch.float64, device=device)
+            self.mean = self._stats[..., 0].view(shape[1:] if normalize == "column" else ())
+            self.std = self._stats[..., 1].view(shape[1:] if normalize == "column" else ())
+        if normalize == "all" and torch.device(device).type == "cuda":
+            need = int(N.load().sgw_returns_workspace_bytes(max(int(shape[0]), 1), cols))
+            self._workspace = torch.empty((need // 8,), dtype=torch.float64, device=device)
+
+    def __repr__(self):
+        return f"Returns(shape={tuple(self.returns.shape)}, normalize={self._mode!r})"
+
+
+def _returns_result(shape, normalize, dtype, device, out):
+    """A fresh ``Returns``, or the caller's ``out`` after checking that it was made for this call's shape and mode."""
+    if normalize not in (None, "column", "all"):
+        raise ValueError(f"normalize must be None, 'column' or 'all', not {normalize!r}")
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"normalised returns are float64 or float32, not {dtype}")
+    if out is None:
+        return Returns(shape, normalize, dtype, device)
+    if not isinstance(out, Returns) or tuple(out.returns.shape) != tuple(shape) or out._mode != normalize or out.returns.device != torch.device(device) \
+            or (normalize is not None and out.normalized.dtype != dtype):
+        raise ValueError(f"out= was not made by a returns() call of shape {tuple(shape)}, normalize={normalize!r}, dtype={dtype} on {device}")
+    return out
+
+
+def _returns_torch(rewards, dones, gamma, first, count, normalize=None, dtype=torch.float64, out=None):
+    """The reference's returns (``sorrel/models/pytorch/ppo.py:226-239``) by torch calls: the path of CPU rings, and what ``sgw_returns`` is
+    compared with and timed against.  ``rewards`` / ``dones`` are ``[capacity, ...]`` views of a ring; the recurrence runs backwards over
+    ``count`` rows from row ``first`` (wrapping), one turn of every column per round, in float32 with the product and the sum rounded
+    separately -- a multiply, then an add -- which is the reference's arithmetic bit for bit."""
+    import warnings
+
+    capacity = int(rewards.shape[0])
+    res = _returns_result((count,) + tuple(rewards.shape[1:]), normalize, dtype, rewards.device, out)
+    g = torch.tensor(gamma, dtype=torch.float32, device=rewards.device)          # NumPy rounds the Python float to float32 as well
+    d = torch.zeros(tuple(rewards.shape[1:]), dtype=torch.float32, device=rewards.device)
+    for t in range(count - 1, -1, -1):
+        row = (first + t) % capacity
+        d = d.masked_fill(dones[row] != 0, 0.0)
+        d = torch.add(rewards[row], torch.mul(d, g), out=res.returns[t])
+    if normalize is not None:
+        x = res.returns.to(torch.float64)
+        dim = 0 if normalize == "column" else None
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")              # (one value: torch warns, and gives NaN as the reference does)
+            mean, std = x.mean(dim=dim), x.std(dim=dim)
+        res.mean.copy_(mean)
+        res.std.copy_(std)
+        res.normalized.copy_((x - mean) / (std + 1e-7))
+    return res
+
+
+def _returns_views(ring, agent):
+    """``rewards`` / ``dones`` of a ring as ``[capacity, columns...]`` views, and how ``sgw_returns`` reads the same columns where they
+    lie: the element offset of column 0 and the (turn, column) strides."""
+    if isinstance(ring, TurnBuffer):
+        E, A = ring.num_envs, ring.obs_shape[0]
+        if agent is None:
+            return ring.rewards, ring.dones, 0, (E * A, 1)
+        if not 0 <= int(agent) < A:
+            raise IndexError(f"agent {agent} outside [0, {A})")
+        return ring.rewards[:, :, int(agent)], ring.dones[:, :, int(agent)], int(agent), (E * A, A)
+    if agent is not None:
+        raise ValueError("a Buffer holds one agent: agent must be None")
+    return ring.rewards, ring.dones, 0, (ring.num_envs, 1)
+
+
+def _ring_returns(ring, agent, gamma, normalize, first, count, dtype, out):
+    """``returns()`` of both ring classes: the segment's defaults and bounds, then ``sgw_returns`` (device ring) or ``_returns_torch``."""
+    import ctypes as C
+
+    cap = ring.capacity
+    full = ring.size >= cap
+    if first is None:
+        first = ring.idx if full else 0
+    if count is None:
+        count = ((ring.idx - first) % cap or cap) if full else max(ring.size - first, 0)          # from `first` to the newest row
+    first, count = int(first), int(count)
+    if not 0 <= first < cap or not 0 <= count <= cap:
+        raise ValueError(f"returns over rows first={first}, count={count} of a ring of {cap}")
+    rewards, dones, offset, (ts, cs) = _returns_views(ring, agent)
+    if ring.device.type != "cuda":
+        return _returns_torch(rewards, dones, gamma, first, count, normalize, dtype, out)
+    from sorrel_amd import _native as N
+
+    for t in (ring.rewards, ring.dones):
+        if not t.is_contiguous():
+            raise ValueError("sgw_returns reads contiguous rings")
+    res = _returns_result((count,) + tuple(rewards.shape[1:]), normalize, dtype, ring.device, out)
+    d = N.SgwReturnsDesc()
+    d.rewards, d.dones = ring.rewards.data_ptr() + 4 * offset, ring.dones.data_ptr() + 4 * offset
+    d.out_returns = res.returns.data_ptr()
+    if normalize is not None:
+        d.out_normalized, d.out_stats = res.normalized.data_ptr(), res._stats.data_ptr()
+    if res._workspace is not None:
+        d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
+    d.first, d.count, d.capacity, d.cols = first, count, cap, int(np.prod(rewards.shape[1:]))
+    d.turn_stride, d.col_stride = ts, cs
+    d.gamma = float(gamma)
+    d.normalize = {None: N.RETURNS_NORM_NONE, "column": N.RETURNS_NORM_COLUMN, "all": N.RETURNS_NORM_ALL}[normalize]
+    d.out_type = N.RETURNS_OUT_F32 if dtype == torch.float32 else N.RETURNS_OUT_F64
+    N.check(N.load().sgw_returns(C.byref(d), C.c_void_p(torch.cuda.current_stream(ring.device).cuda_stream)))
+    return res
+
+
 class Buffer:
     """``extra`` keyword arguments declare additional int64 columns exactly as in the reference
     (``Buffer(capacity, obs_shape, positions=(2,))``, ``sorrel/buffers.py:39-44``): a tuple gives the trailing
@@ -348,8 +470,38 @@ class Buffer:
         return _sample_fresh(_ring_layout(self, None), self.n_frames, batch_size, t0, e,
                              self.capacity - self.n_frames if given else max(1, self.size - self.n_frames - 1))
 
+    def returns(self, gamma: float, normalize=None, first=None, count=None, dtype=torch.float64, out=None) -> Returns:
+        """Discounted returns of every env's stored turns, as the reference's PPO computes them at the head of ``train_step``
+        (``sorrel/models/pytorch/ppo.py:226-239``): backwards in time, ``d = 0`` at every ``done``, ``d = reward + gamma * d`` in
+        float32.  The segment defaults to everything stored, oldest to newest: rows ``0 .. size`` before the ring has wrapped,
+        ``idx .. idx + capacity`` (mod ``capacity``) after; ``first`` / ``count`` name another one.  ``normalize="column"`` adds the
+        reference's ``(x - mean) / (std + 1e-7)`` in float64 per env, ``"all"`` with one mean / std over the whole segment; ``dtype`` is
+        the type the normalised values are stored in.  On a HIP device this is one ``sgw_returns`` call that reads the ring where it
+        lies; with ``out=`` (an earlier result of the same shape and mode) it allocates nothing and does not synchronise, so it
+        can be recorded into a graph."""
+        return _ring_returns(self, None, gamma, normalize, first, count, dtype, out)
+
     def __repr__(self):
         return f"Buffer(capacity={self.capacity}, obs_shape={self.obs_shape}, num_envs={self.num_envs})"
+
+
+class RolloutBuffer(Buffer):
+    """The reference's ``RolloutBuffer`` (``sorrel/models/pytorch/ppo.py:21-65``) for all envs at once: a ``Buffer`` with a float32
+    ``log_probs`` column ``[capacity, E]``, whose ``add`` takes the action as an ``(action, log_prob)`` pair.  ``returns()`` is what a
+    policy-gradient learner opens its update with."""
+
+    def __init__(self, capacity: int, obs_shape: Sequence[int], n_frames: int = 1, num_envs: int = 1, device=None, **extra):
+        super().__init__(capacity, obs_shape, n_frames, num_envs, device, **extra)
+        self.log_probs = torch.zeros((capacity, num_envs), dtype=torch.float32, device=self.device)
+
+    def clear(self):
+        super().clear()
+        self.log_probs.zero_()
+
+    def add(self, obs, action, reward, done, **extra):
+        action_, log_prob = action
+        self.log_probs[self.idx] = torch.as_tensor(log_prob, dtype=torch.float32, device=self.device)
+        super().add(obs, action_, reward, done, **extra)
 
 
 class SavedGames(Buffer):
@@ -446,6 +598,11 @@ class TurnBuffer:
             st, ac, rw, dn = self.agent_view(int(agent))
         s, a, r, ns, d, v = _stack_torch(st, ac, rw, dn, n_frames, batch_size, t0, e)
         return s.to(torch.float32), a.to(torch.int64), r, ns.to(torch.float32), d, v
+
+    def returns(self, gamma: float, agent=None, normalize=None, first=None, count=None, dtype=torch.float64, out=None) -> Returns:
+        """``Buffer.returns`` over the joint ring, read where it lies: ``agent=None`` runs over every (env, agent) column (``returns``
+        ``[count, E, A]``, ``normalize="column"`` per env and agent), ``agent=a`` over that agent's columns (``[count, E]``)."""
+        return _ring_returns(self, agent, gamma, normalize, first, count, dtype, out)
 
     def clear(self):
         self.idx = self.size = 0

@@ -70,6 +70,7 @@ namespace {
 #include "resolve.h"
 #include "render.h"
 #include "sample.h"
+#include "returns.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -1298,6 +1299,61 @@ int sgw_sample(const sgw_sample_desc* d, void* stream) {
     HIP_TRY(hipGetLastError());
     if (!d->starts && d->draw_count) {
         hipLaunchKernelGGL(sample_count_kernel, dim3(1), dim3(64), 0, s, d->draw_count);
+        HIP_TRY(hipGetLastError());
+    }
+    return SGW_OK;
+}
+
+// ---------------------------------------------------------------- discounted returns (returns.h)
+int64_t sgw_returns_workspace_bytes(int64_t count, int64_t cols) {
+    if (count < 0) return fail(SGW_EINVAL, "sgw_returns_workspace_bytes: count = %lld", (long long)count);
+    if (cols < 1 || cols >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_returns_workspace_bytes: cols = %lld outside [1, 2^31)", (long long)cols);
+    return count == 0 ? 0 : returns_blocks(cols) * 3 * (int64_t)sizeof(double);
+}
+
+int sgw_returns(const sgw_returns_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_returns: desc is NULL");
+    if (!d->rewards || !d->dones || !d->out_returns) return fail(SGW_EINVAL, "sgw_returns: rewards, dones and out_returns must not be NULL");
+    if (d->normalize != SGW_RETURNS_NORM_NONE && d->normalize != SGW_RETURNS_NORM_COLUMN && d->normalize != SGW_RETURNS_NORM_ALL)
+        return fail(SGW_EINVAL, "sgw_returns: unknown normalize %d", d->normalize);
+    if (d->out_type != SGW_RETURNS_OUT_F64 && d->out_type != SGW_RETURNS_OUT_F32) return fail(SGW_EINVAL, "sgw_returns: unknown out_type %d", d->out_type);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "sgw_returns: reserved fields must be 0");
+    const bool norm = d->normalize != SGW_RETURNS_NORM_NONE, out32 = d->out_type == SGW_RETURNS_OUT_F32;
+    if (norm && !d->out_normalized) return fail(SGW_EINVAL, "sgw_returns: normalize = %d needs out_normalized", d->normalize);
+    if (d->capacity < 1) return fail(SGW_EINVAL, "sgw_returns: capacity = %lld", (long long)d->capacity);
+    if (d->count < 0 || d->count > d->capacity) return fail(SGW_EINVAL, "sgw_returns: count = %lld outside [0, capacity = %lld]", (long long)d->count, (long long)d->capacity);
+    if (d->first < 0 || d->first >= d->capacity) return fail(SGW_EINVAL, "sgw_returns: first = %lld outside [0, capacity = %lld)", (long long)d->first, (long long)d->capacity);
+    if (d->cols < 1 || d->cols >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_returns: cols = %lld outside [1, 2^31)", (long long)d->cols);
+    if (d->turn_stride < 1 || d->col_stride < 1) return fail(SGW_EINVAL, "sgw_returns: turn_stride = %lld, col_stride = %lld: strides must be at least 1", (long long)d->turn_stride, (long long)d->col_stride);
+    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    if ((at(d->rewards) | at(d->dones) | at(d->out_returns) | (out32 ? at(d->out_normalized) : 0)) & 3) return fail(SGW_EINVAL, "sgw_returns: misaligned float32 pointer");
+    if (((out32 ? 0 : at(d->out_normalized)) | at(d->out_stats) | at(d->workspace)) & 7) return fail(SGW_EINVAL, "sgw_returns: misaligned float64 pointer");
+    // the largest element offset read, capacity * turn_stride + cols * col_stride, and the largest byte offset written, 8 * count * cols
+    if (d->capacity > INT64_MAX / 2 / d->turn_stride || d->cols > INT64_MAX / 2 / d->col_stride || d->count > INT64_MAX / 16 / d->cols)
+        return fail(SGW_EINVAL, "sgw_returns: capacity = %lld, cols = %lld with strides %lld / %lld do not fit 64-bit offsets", (long long)d->capacity, (long long)d->cols, (long long)d->turn_stride, (long long)d->col_stride);
+    const unsigned blocks = (unsigned)returns_blocks(d->cols);
+    if (d->normalize == SGW_RETURNS_NORM_ALL) {
+        const int64_t need = (int64_t)blocks * 3 * (int64_t)sizeof(double);
+        if (!d->workspace || d->workspace_bytes < need)
+            return fail(SGW_EINVAL, "sgw_returns: SGW_RETURNS_NORM_ALL needs a workspace of %lld bytes (sgw_returns_workspace_bytes); got %lld", (long long)need, d->workspace ? (long long)d->workspace_bytes : 0ll);
+    }
+    if (d->count == 0) return SGW_OK;
+    ReturnsParams p{};
+    p.rewards = d->rewards; p.dones = d->dones; p.out_returns = d->out_returns; p.out_norm = d->out_normalized; p.out_stats = d->out_stats;
+    p.partials = static_cast<double*>(d->workspace);
+    p.first = d->first; p.count = d->count; p.capacity = d->capacity; p.cols = d->cols; p.ts = d->turn_stride; p.cs = d->col_stride;
+    p.tiles = ceil_div(d->cols, kBlock);
+    p.gamma = (float)d->gamma;                  // round to nearest even: what NumPy does with a Python float next to float32 data
+    p.nparts = (int32_t)blocks;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (d->normalize == SGW_RETURNS_NORM_NONE) launch_returns<SGW_RETURNS_NORM_NONE>(p, false, blocks, s);
+    else if (d->normalize == SGW_RETURNS_NORM_COLUMN) launch_returns<SGW_RETURNS_NORM_COLUMN>(p, out32, blocks, s);
+    else launch_returns<SGW_RETURNS_NORM_ALL>(p, false, blocks, s);
+    HIP_TRY(hipGetLastError());
+    if (d->normalize == SGW_RETURNS_NORM_ALL) {
+        const unsigned nblocks = (unsigned)std::min<int64_t>(ceil_div(d->count * d->cols, kBlock * 4), kReturnsMaxBlocks);
+        if (out32) hipLaunchKernelGGL((returns_normalize_all_kernel<true>), dim3(nblocks), dim3(kBlock), 0, s, p);
+        else hipLaunchKernelGGL((returns_normalize_all_kernel<false>), dim3(nblocks), dim3(kBlock), 0, s, p);
         HIP_TRY(hipGetLastError());
     }
     return SGW_OK;

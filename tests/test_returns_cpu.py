@@ -1,0 +1,231 @@
+"""Discounted returns without a GPU: the declaration of ``sgw_returns`` and its ctypes mirror, every descriptor the call rejects (validation
+precedes the launch, so no device is needed), ``RolloutBuffer`` against the reference's behaviour, and ``returns()`` of the three rings on
+the CPU against what the reference's ``PyTorchPPO.train_step`` computed (``tests/golden/returns``): raw returns bit for bit, normalised
+values within the derived tolerance, on wrapped and unwrapped segments."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from sorrel_amd import _native as N
+from sorrel_amd.buffers import Buffer, Returns, RolloutBuffer, TurnBuffer, _returns_torch
+from tests import helpers as H
+from tests import returns_common as RC
+
+
+# ------------------------------------------------------------------------------------------------------------- header and binding
+def test_header_declares_sgw_returns_and_the_binding_mirrors_it(built):
+    text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
+    assert re.search(r"int sgw_returns\(const sgw_returns_desc\* desc, void\* stream\);", text)
+    assert re.search(r"int64_t sgw_returns_workspace_bytes\(int64_t count, int64_t cols\);", text)
+    assert "sgw_returns" in N.EXPORTS and "sgw_returns_workspace_bytes" in N.EXPORTS
+    macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)\b", text)}
+    assert (N.RETURNS_NORM_NONE, N.RETURNS_NORM_COLUMN, N.RETURNS_NORM_ALL, N.RETURNS_OUT_F64, N.RETURNS_OUT_F32) == tuple(
+        macros[k] for k in ("SGW_RETURNS_NORM_NONE", "SGW_RETURNS_NORM_COLUMN", "SGW_RETURNS_NORM_ALL", "SGW_RETURNS_OUT_F64", "SGW_RETURNS_OUT_F32"))
+    body = re.search(r"typedef struct sgw_returns_desc \{(.*?)\} sgw_returns_desc;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [f.split("*")[-1].split()[-1] for decl in body.split(";") if decl.strip() for f in decl.split(",")]
+    assert fields == [name for name, _ in N.SgwReturnsDesc._fields_]
+    # 6 pointers, 7 int64 (workspace_bytes, first, count, capacity, cols, two strides), 1 double, 4 int32
+    assert C.sizeof(N.SgwReturnsDesc) == 6 * 8 + 7 * 8 + 8 + 4 * 4
+    assert N.SgwReturnsDesc.gamma.offset == 13 * 8 and N.SgwReturnsDesc.normalize.offset == 14 * 8
+    lib = N.load()
+    assert hasattr(lib, "sgw_returns") and hasattr(lib, "sgw_returns_workspace_bytes")
+    assert lib.sgw_version() == b"sgw 0.3 (gfx950)"                # the addition is append-only
+    assert RC.chunk() >= 2 and RC.max_blocks() >= 2
+
+
+def good_desc():
+    """A descriptor the call accepts (the pointers are never followed: every test below is rejected, or has count == 0)."""
+    d = N.SgwReturnsDesc()
+    d.rewards = d.dones = d.out_returns = d.out_normalized = 4096
+    d.first, d.count, d.capacity, d.cols = 3, 0, 16, 5
+    d.turn_stride, d.col_stride = 5, 1
+    d.gamma = 0.97
+    d.normalize, d.out_type = N.RETURNS_NORM_COLUMN, N.RETURNS_OUT_F64
+    return d
+
+
+REJECTED = (
+    [(f"{name} is NULL", {name: None}, b"must not be NULL") for name in ("rewards", "dones", "out_returns")]
+    + [
+        ("count < 0", {"count": -1}, b"count"),
+        ("count > capacity", {"count": 17}, b"count"),
+        ("capacity < 1", {"capacity": 0, "first": 0, "count": 0}, b"capacity"),
+        ("first < 0", {"first": -1}, b"first"),
+        ("first == capacity", {"first": 16}, b"first"),
+        ("cols < 1", {"cols": 0}, b"cols"),
+        ("cols >= 2^31", {"cols": 1 << 31}, b"cols"),
+        ("turn_stride < 1", {"turn_stride": 0}, b"stride"),
+        ("col_stride < 1", {"col_stride": -1}, b"stride"),
+        ("unknown normalize", {"normalize": 3}, b"normalize"),
+        ("negative normalize", {"normalize": -1}, b"normalize"),
+        ("unknown out_type", {"out_type": 2}, b"out_type"),
+        ("reserved0 set", {"reserved0": 1}, b"reserved"),
+        ("reserved1 set", {"reserved1": 1}, b"reserved"),
+        ("NORM_COLUMN without out_normalized", {"out_normalized": None}, b"out_normalized"),
+        ("NORM_ALL without out_normalized", {"normalize": N.RETURNS_NORM_ALL, "out_normalized": None, "workspace": 4096, "workspace_bytes": 1 << 20}, b"out_normalized"),
+        ("NORM_ALL without a workspace", {"normalize": N.RETURNS_NORM_ALL}, b"workspace"),
+        ("NORM_ALL with a short workspace", {"normalize": N.RETURNS_NORM_ALL, "workspace": 4096, "workspace_bytes": 23}, b"workspace"),
+        ("NORM_ALL with a short workspace for many columns", {"normalize": N.RETURNS_NORM_ALL, "cols": 600, "turn_stride": 600, "workspace": 4096, "workspace_bytes": 3 * 24 - 1}, b"workspace"),
+        ("misaligned rewards", {"rewards": 4098}, b"float32"),
+        ("misaligned dones", {"dones": 4097}, b"float32"),
+        ("misaligned out_returns", {"out_returns": 4099}, b"float32"),
+        ("misaligned float32 out_normalized", {"out_normalized": 4098, "out_type": N.RETURNS_OUT_F32}, b"float32"),
+        ("misaligned float64 out_normalized", {"out_normalized": 4100}, b"float64"),
+        ("misaligned out_stats", {"out_stats": 4100}, b"float64"),
+        ("misaligned workspace", {"normalize": N.RETURNS_NORM_ALL, "workspace": 4100, "workspace_bytes": 1 << 20}, b"float64"),
+        ("turn offsets overflow", {"capacity": 1 << 40, "turn_stride": 1 << 40}, b"64-bit"),
+        ("column offsets overflow", {"cols": (1 << 31) - 1, "col_stride": 1 << 40}, b"64-bit"),
+        ("output offsets overflow", {"capacity": 1 << 60, "count": 1 << 59, "cols": 1 << 30, "turn_stride": 1}, b"64-bit"),
+    ]
+)
+
+
+@pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
+def test_sgw_returns_rejects(built, case):
+    _, change, word = case
+    lib = N.load()
+    d = good_desc()
+    d.count = 5                                   # (a call that would launch, were it accepted)
+    for key, value in change.items():
+        setattr(d, key, value)
+    assert lib.sgw_returns(C.byref(d), None) == N.EINVAL
+    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+
+
+def test_sgw_returns_null_desc_no_turns_and_the_workspace_size(built):
+    lib = N.load()
+    assert lib.sgw_returns(None, None) == N.EINVAL and b"desc is NULL" in lib.sgw_last_error()
+    d = good_desc()
+    assert lib.sgw_returns(C.byref(d), None) == N.OK              # count == 0: nothing is launched
+    d.normalize, d.out_normalized = N.RETURNS_NORM_NONE, None     # no normalisation needs no second output
+    assert lib.sgw_returns(C.byref(d), None) == N.OK
+    d.out_normalized, d.out_type = 4100, N.RETURNS_OUT_F32        # float32 values need 4-byte alignment only
+    d.normalize = N.RETURNS_NORM_COLUMN
+    assert lib.sgw_returns(C.byref(d), None) == N.OK
+    d.normalize, d.workspace, d.workspace_bytes = N.RETURNS_NORM_ALL, 4096, 24
+    assert lib.sgw_returns(C.byref(d), None) == N.OK
+    # one partial of three doubles per workgroup of 256 columns, up to the grid cap; nothing for no turns
+    size = lib.sgw_returns_workspace_bytes
+    assert size(100, 1) == size(1, 256) == 24 and size(7, 257) == 48 and size(7, 600) == 72 and size(0, 600) == 0
+    assert size(3, (1 << 31) - 1) == 24 * RC.max_blocks() == size(3, 256 * RC.max_blocks())
+    for count, cols in ((-1, 5), (5, 0), (5, 1 << 31)):
+        assert size(count, cols) == N.EINVAL
+
+
+# ------------------------------------------------------------------------------------------------------------- RolloutBuffer
+def test_rollout_buffer_behaves_as_the_reference(tmp_path):
+    """``sorrel/models/pytorch/ppo.py:21-65``: a Buffer plus ``log_probs``; ``add`` takes ``(action, log_prob)``; ``clear`` zeroes the column."""
+    buf = RolloutBuffer(4, (2, 3), num_envs=3, device="cpu")
+    assert isinstance(buf, Buffer) and buf.log_probs.dtype == torch.float32 and tuple(buf.log_probs.shape) == (4, 3)
+    assert not buf.log_probs.any()
+    for i in range(6):                                              # wraps: rows 0 and 1 are overwritten by turns 4 and 5
+        obs = torch.full((3, 2, 3), float(i))
+        buf.add(obs, (torch.tensor([i, i + 1, i + 2]), torch.tensor([-0.1 * i, -0.2 * i, -0.3 * i])), torch.tensor([1.0, 2.0, 3.0]) * i, i == 3)
+    assert buf.idx == 2 and buf.size == 4 and len(buf) == 4
+    turns = [4, 5, 2, 3]
+    assert buf.actions[:, 0].tolist() == turns and buf.rewards[:, 2].tolist() == [3.0 * t for t in turns]
+    assert np.array_equal(buf.log_probs.numpy(), np.float32([[-0.1 * t, -0.2 * t, -0.3 * t] for t in turns]))
+    assert buf.dones[:, 1].tolist() == [0.0, 0.0, 0.0, 1.0] and buf.states[1, 2, 1, 1] == 5.0
+    buf.add(torch.zeros(3, 2, 3), (0, 0.25), 0.0, False)            # scalars broadcast over the envs, as every column of add does
+    assert buf.log_probs[2].tolist() == [0.25] * 3
+    path = tmp_path / "rollout.npz"
+    buf.save(path)                                                  # save / load are the Buffer's
+    again = RolloutBuffer.load(path)
+    assert isinstance(again, RolloutBuffer) and torch.equal(again.rewards, buf.rewards) and not again.log_probs.any()
+    buf.clear()
+    assert buf.idx == buf.size == 0 and not buf.log_probs.any() and not buf.rewards.any() and not buf.dones.any()
+
+
+# ------------------------------------------------------------------------------------------------------------- the CPU rings
+FIX = RC.load_fixture()
+IDS = [f"T{f['T']}-gamma{f['gamma']}" for f in FIX]
+
+
+def check_against_fixture(res, cols, f, ctx):
+    """Columns ``cols`` of a ``Returns`` ``[T, n]`` carry the fixture trajectory: raw returns equal, normalised within the column tolerance."""
+    assert isinstance(res, Returns) and res.returns.dtype == torch.float32 and res.normalized.dtype == torch.float64
+    raw = res.returns.reshape(f["T"], -1).numpy()
+    norm = res.normalized.reshape(f["T"], -1).numpy()
+    for c in cols:
+        assert np.array_equal(raw[:, c], f["returns"]), f"{ctx}: raw returns of column {c} differ from the reference's"
+        if f["T"] == 1:
+            assert np.isnan(norm[:, c]).all() and np.isnan(f["normalized"]).all(), f"{ctx}: one stored element normalises to NaN"
+        else:
+            RC.assert_normalized(norm[:, c], f["normalized"], RC.tolerance(f["returns"]), f"{ctx}: column {c}")
+            mean, std = RC.host_stats(f["returns"])
+            assert abs(float(res.mean.reshape(-1)[c]) - mean) <= 8 * f["T"] * 2.0 ** -53 * np.abs(f["returns"]).max()
+            assert abs(float(res.std.reshape(-1)[c]) - std) <= 8 * f["T"] * 2.0 ** -53 * (std + np.abs(f["returns"]).max())
+
+
+@pytest.mark.parametrize("f", FIX, ids=IDS)
+@pytest.mark.parametrize("wrapped", [False, True], ids=["unwrapped", "wrapped"])
+def test_returns_on_cpu_rings_against_the_reference(f, wrapped):
+    T, E, A = f["T"], 5, 3
+    rng = np.random.default_rng(T)
+    cap = T if wrapped else T + 3
+    first = (T * 2) // 3 if wrapped else 0
+    # Buffer and RolloutBuffer: the trajectory in envs 0 and 3
+    for cls in (Buffer, RolloutBuffer):
+        rewards, dones = RC.ring_arrays(rng, cap, E, first, T, [(0, f["rewards"], f["dones"]), (3, f["rewards"], 7.0 * f["dones"])])
+        buf = cls(cap, (2,), num_envs=E, device="cpu")
+        buf.rewards.copy_(torch.from_numpy(rewards))
+        buf.dones.copy_(torch.from_numpy(dones))
+        buf.idx, buf.size = (first, cap) if wrapped else (T, T)
+        res = buf.returns(f["gamma"], normalize="column")
+        assert tuple(res.returns.shape) == (T, E) and tuple(res.mean.shape) == (E,)
+        check_against_fixture(res, (0, 3), f, f"{cls.__name__} wrapped={wrapped}")
+        # the same segment named explicitly, without normalisation, into the earlier result's storage
+        raw = buf.returns(f["gamma"], first=first, count=T)
+        assert raw.normalized is None and raw.mean is None and torch.equal(raw.returns, res.returns)
+        kept = res.returns.data_ptr()
+        assert buf.returns(f["gamma"], normalize="column", out=res) is res and res.returns.data_ptr() == kept
+        # the other columns: the torch restatement IS the CPU path
+        want = _returns_torch(buf.rewards, buf.dones, f["gamma"], first, T)
+        assert torch.equal(want.returns, res.returns)
+    # TurnBuffer: the trajectory in (env 1, agent 2) and (env 4, agent 0); every agent at once and one agent
+    rewards, dones = RC.ring_arrays(rng, cap, E * A, first, T, [(1 * A + 2, f["rewards"], f["dones"]), (4 * A + 0, f["rewards"], f["dones"])])
+    ring = TurnBuffer(cap, E, (A, 1, 1, 1), device="cpu")
+    ring.rewards.copy_(torch.from_numpy(rewards).view(cap, E, A))
+    ring.dones.copy_(torch.from_numpy(dones).view(cap, E, A))
+    ring.idx, ring.size = (first, cap) if wrapped else (T, T)
+    res = ring.returns(f["gamma"], normalize="column")
+    assert tuple(res.returns.shape) == (T, E, A) and tuple(res.std.shape) == (E, A)
+    check_against_fixture(res, (1 * A + 2, 4 * A + 0), f, f"TurnBuffer agent=None wrapped={wrapped}")
+    one = ring.returns(f["gamma"], agent=2, normalize="column")
+    assert tuple(one.returns.shape) == (T, E) and torch.equal(one.returns, res.returns[:, :, 2])
+    check_against_fixture(one, (1,), f, f"TurnBuffer agent=2 wrapped={wrapped}")
+    check_against_fixture(ring.returns(f["gamma"], agent=0, normalize="column"), (4,), f, f"TurnBuffer agent=0 wrapped={wrapped}")
+    # one mean / std over the segment, float64 and float32, against host statistics by math.fsum
+    for dtype in (torch.float64, torch.float32):
+        whole = ring.returns(f["gamma"], normalize="all", dtype=dtype)
+        assert torch.equal(whole.returns, res.returns) and whole.normalized.dtype == dtype and whole.mean.dim() == 0
+        x = res.returns.reshape(T, -1).numpy()
+        want, mean, std = RC.host_normalized(x, "all")
+        RC.assert_normalized(whole.normalized.reshape(T, -1).numpy(), want, RC.tolerance(x), f"normalize='all' {dtype}")
+
+
+def test_returns_arguments_are_checked():
+    buf = Buffer(6, (2,), num_envs=2, device="cpu")
+    ring = TurnBuffer(6, 2, (3, 1, 1, 1), device="cpu")
+    assert tuple(buf.returns(0.9).returns.shape) == (0, 2)         # nothing stored: an empty segment
+    buf.size = buf.idx = 4
+    assert tuple(buf.returns(0.9).returns.shape) == (4, 2) and tuple(buf.returns(0.9, first=1).returns.shape) == (3, 2)
+    with pytest.raises(ValueError):
+        buf.returns(0.9, normalize="rows")
+    with pytest.raises(TypeError):
+        buf.returns(0.9, normalize="all", dtype=torch.float16)
+    with pytest.raises(ValueError):
+        buf.returns(0.9, first=6)
+    with pytest.raises(ValueError):
+        buf.returns(0.9, count=7)
+    with pytest.raises(ValueError):
+        buf.returns(0.9, out=buf.returns(0.9, normalize="column"))  # made for another mode
+    with pytest.raises(ValueError):
+        buf.returns(0.9, count=2, out=buf.returns(0.9))             # ... another shape
+    with pytest.raises(IndexError):
+        ring.returns(0.9, agent=3)
