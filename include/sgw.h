@@ -108,6 +108,7 @@ extern "C" {
 #define SGW_STREAM_VALUE 8             /* index = layer-major cell index of the TARGET cell (the spawn stream's index), turn = the turn in
                                         * flight: which of its two values a type with value_alt_prob > 0 is worth this turn */
 #define SGW_STREAM_SAMPLE 9            /* sgw_sample's drawn indices: epoch 0, turn / env = the low / high word of the draw counter */
+#define SGW_STREAM_POLICY 10u          /* (unsigned, as the flags are: it is or-ed into a 32-bit counter word) index = agent, turn = the turn in flight: the uniform sgw_policy_sample draws an action with (SGW_STREAM_EXPLORE's layout) */
 
 /* what Agent.act does (sgw_config.agent_rule) */
 #define SGW_AGENT_RULE_MOVE 0 /* MovingAgent.act: reward = value of the target, then move (sorrel/agents/agent.py:215-225) */
@@ -702,6 +703,60 @@ typedef struct sgw_returns_desc {
 int sgw_returns(const sgw_returns_desc* desc, void* stream);
 /* Bytes of workspace SGW_RETURNS_NORM_ALL needs for this shape (0 for no turns); a negative code for a shape sgw_returns rejects. */
 int64_t sgw_returns_workspace_bytes(int64_t count, int64_t cols);
+
+/* ---- stochastic policies (sorrel/models/pytorch/ppo.py:121-137: ActorCritic.act -- Categorical(probs).sample() and .log_prob() --
+ * and :139-152, evaluate's .entropy(); for a batch of distributions, on the device) ----
+ * One launch turns n rows of num_actions numbers into an action, its log-probability and the row's entropy.  1 <= num_actions <= 256
+ * (beyond SGW_MAX_ACTIONS: the call needs no engine).  The numbers are float32 or float64 (dist_type), probabilities or logits (mode).
+ * All arithmetic is float64, sequential in index order: no re-association, and no fused multiply-add where one would change a result.
+ *   weights    SGW_POLICY_PROBS:   w_i = (double)x_i -- unnormalised, as Categorical(probs=...) accepts them
+ *              SGW_POLICY_LOGITS:  w_i = exp((double)x_i - max_j x_j); -inf gives 0
+ *              S = ((w_0 + w_1) + ...)
+ *   invalid    a row is invalid if any w_i is negative or NaN, if S is 0 or not finite, or if the maximum logit is NaN or +inf (torch
+ *              raises for such a row): it gets action 255, which no ActionSpec has (SGW_STATUS_BAD_ACTION if played), and NaN for its
+ *              log-probability and entropy.  So does a row whose `idx` entry names no (env, agent) pair: idx[k] < 0 or
+ *              idx[k] / num_envs >= SGW_MAX_AGENTS.  Other rows are untouched by it.
+ *   draw       u = Philox4x32-10(ctr = {agent >> 2, turn, first_env + env, epoch << 4 | SGW_STREAM_POLICY}, key = {seed lo, seed hi})[agent & 3]
+ *              -- the layout of SGW_STREAM_EXPLORE; `turn` is the turn in flight, as for the exploration draw.  The draw is keyed, not
+ *              consumed: a row's action is a function of (its numbers, seed, env, epoch, turn, agent).
+ *   action     t = ((double)u + 0.5) * 2^-32 * S; the action is the first i with c_i > t, where c_i = c_(i-1) + w_i is the running sum in
+ *              the same order.  A zero-weight action can never be chosen; t < S always holds, so a valid row always finds one.
+ *   log-prob,  torch's Categorical, its clamp included: q_i = w_i / S; l_i = log(min(max(q_i, 2^-52), 1 - 2^-52));
+ *   entropy    log_prob = (float)l_action; entropy = (float)(-((q_0 * l_0 + q_1 * l_1) + ...)), every product rounded before it is added.
+ *              The float32 value is the float64 value rounded once: what the reference's log_probs[idx] = log_prob stores.
+ * Row k starts at element k * row_stride of `dist` and is keyed as (env, agent) = (idx[k] % num_envs, idx[k] / num_envs), or with
+ * idx == NULL as (k % num_envs, agent0 + k / num_envs): one agent's [E] rows and a shared model's agent-major [A * E] rows alike (the row
+ * numbering of sgw_choose_actions); idx may repeat and reorder.  out_log_probs / out_entropy may be NULL (nothing is computed for them).
+ * Needs no engine; all pointers are device pointers.  Asynchronous on `stream`; everything the host can see -- NULL dist or out_actions,
+ * n < 0, num_actions outside 1..256, num_envs < 1, row_stride < num_actions, an agent key outside [0, SGW_MAX_AGENTS) with idx == NULL,
+ * epoch >= 2^28, an unknown dist_type or mode, a misaligned pointer, n * row_stride beyond 64-bit offsets, a non-zero reserved field -- is
+ * SGW_EINVAL with the reason in sgw_last_error(), before anything is launched.  n == 0 launches nothing. */
+#define SGW_POLICY_F32 0         /* dist_type: the rows are float32 */
+#define SGW_POLICY_F64 1         /* ... float64 */
+#define SGW_POLICY_PROBS 0       /* mode: unnormalised probabilities */
+#define SGW_POLICY_LOGITS 1      /* ... logits */
+#define SGW_POLICY_MAX_ACTIONS 256
+typedef struct sgw_policy_desc {
+    const void* dist;            /* [n] rows of num_actions elements of dist_type, row_stride elements apart */
+    const int64_t* idx;          /* [n] row keys agent * num_envs + env, or NULL */
+    int64_t* out_actions;        /* [n] */
+    float* out_log_probs;        /* [n], or NULL */
+    float* out_entropy;          /* [n], or NULL */
+    int64_t n, num_envs, row_stride;
+    uint64_t seed, first_env;    /* first_env: the global id of env 0 (sgw_config.first_env_id); its low 32 bits enter the counter */
+    uint32_t epoch, turn;
+    int32_t num_actions, agent0, dist_type, mode;
+    int32_t reserved0, reserved1;    /* reserved: 0 */
+} sgw_policy_desc;
+int sgw_policy_sample(const sgw_policy_desc* desc, void* stream);
+/* The same kernel under the turn protocol (sgw_turn_*): agent `agent`'s [E][num_actions] rows (contiguous; num_actions = the engine's) are
+ * sampled with the engine's seed and first_env_id, and with epoch and the turn in flight (= completed + 1) read from the device's turn
+ * state, as sgw_turn_act reads them.  log_prob_ring is the base of a float32 [capacity][E] ring (capacity = the agent's bound ring's) or
+ * NULL: the kernel writes row ts->row[agent] of it -- the row the turn in flight fills.  out_actions int64 [E] (what sgw_turn_act takes as
+ * SGW_ACT_I64), out_entropy float32 [E] or NULL.  Same arguments every turn: recordable.  SGW_EINVAL when a ring is given and the agent
+ * has no bound replay rows (sgw_turn_bind). */
+int sgw_turn_policy_sample(sgw_engine* eng, int32_t agent, const void* dist, int32_t dist_type, int32_t mode, int64_t* out_actions,
+                           float* log_prob_ring, float* out_entropy, void* stream);
 
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */

@@ -31,6 +31,11 @@ SAMPLE_F32, SAMPLE_U8 = 0, 1
 SAMPLE_ACT_I64, SAMPLE_ACT_U8 = 0, 1
 RETURNS_NORM_NONE, RETURNS_NORM_COLUMN, RETURNS_NORM_ALL = 0, 1, 2
 RETURNS_OUT_F64, RETURNS_OUT_F32 = 0, 1
+STREAM_POLICY = 10          # sgw_policy_sample's draw: index = agent, turn = the turn in flight (STREAM_EXPLORE's layout)
+POLICY_F32, POLICY_F64 = 0, 1
+POLICY_PROBS, POLICY_LOGITS = 0, 1
+POLICY_MAX_ACTIONS = 256
+POLICY_INVALID_ACTION = 255  # the action of a row torch's Categorical would raise for (its log-probability and entropy are NaN)
 
 
 class SgwConfig(C.Structure):
@@ -156,6 +161,19 @@ class SgwReturnsDesc(C.Structure):
     ]
 
 
+class SgwPolicyDesc(C.Structure):
+    """Mirror of ``struct sgw_policy_desc`` (include/sgw.h): one ``sgw_policy_sample`` call; layout checked by tests/test_policy_cpu.py."""
+
+    _fields_ = [
+        ("dist", C.c_void_p), ("idx", C.c_void_p), ("out_actions", C.c_void_p), ("out_log_probs", C.c_void_p), ("out_entropy", C.c_void_p),
+        ("n", C.c_int64), ("num_envs", C.c_int64), ("row_stride", C.c_int64),
+        ("seed", C.c_uint64), ("first_env", C.c_uint64),
+        ("epoch", C.c_uint32), ("turn", C.c_uint32),
+        ("num_actions", C.c_int32), ("agent0", C.c_int32), ("dist_type", C.c_int32), ("mode", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -168,6 +186,7 @@ EXPORTS = (
     "sgw_set_option", "sgw_plan", "sgw_jit_stats", "sgw_jit_compile", "sgw_bind_row_tail",
     "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render", "sgw_sample",
     "sgw_returns", "sgw_returns_workspace_bytes",
+    "sgw_policy_sample", "sgw_turn_policy_sample",
     "sgw_last_error", "sgw_version",
 )
 
@@ -313,6 +332,10 @@ def load():
     lib.sgw_returns.restype = C.c_int
     lib.sgw_returns_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.sgw_returns_workspace_bytes.restype = C.c_int64
+    lib.sgw_policy_sample.argtypes = [C.POINTER(SgwPolicyDesc), vp]
+    lib.sgw_policy_sample.restype = C.c_int
+    lib.sgw_turn_policy_sample.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.sgw_turn_policy_sample.restype = C.c_int
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

@@ -107,10 +107,11 @@ class Agent(Entity):
         state = self.pov(world)
         action = self.get_action(state)
         reward = self.act(world, action)
-        if torch.is_tensor(action) and action.dim() == 2:
+        if not torch.is_tensor(action) or action.dim() == 2:
             # get_action returned action VALUES ([E, n_actions]): the act chose -- argmax, or the engine's uniform draw with
-            # probability ``epsilon`` (iqn.py:294-309, in-kernel) -- and what it took is on record
-            action = world._environment.actions[:, self.slot]
+            # probability ``epsilon`` (iqn.py:294-309, in-kernel) -- and what it took is on record; or a distribution (ActionProbs /
+            # ActionLogits): the engine sampled it (ppo.py:121-137), and a RolloutBuffer receives (action, log_prob)
+            action = world._environment._memory_action(self, action)
         done = self.is_done(world)
         self.add_memory(state, action, reward, done)
 

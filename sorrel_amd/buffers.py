@@ -500,7 +500,12 @@ class RolloutBuffer(Buffer):
 
     def add(self, obs, action, reward, done, **extra):
         action_, log_prob = action
-        self.log_probs[self.idx] = torch.as_tensor(log_prob, dtype=torch.float32, device=self.device)
+        # a recorded turn only counts (the engine's own kernels fill the row, by the device's row count: sgw_turn_policy_sample); and
+        # log-probabilities the sampling launch has already written into this row are not copied again
+        if not self._deferred:
+            row = self.log_probs[self.idx]
+            if not (torch.is_tensor(log_prob) and log_prob.dtype == torch.float32 and log_prob.data_ptr() == row.data_ptr()):
+                self.log_probs[self.idx] = torch.as_tensor(log_prob, dtype=torch.float32, device=self.device)
         super().add(obs, action_, reward, done, **extra)
 
 

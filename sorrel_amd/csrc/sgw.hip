@@ -71,6 +71,7 @@ namespace {
 #include "render.h"
 #include "sample.h"
 #include "returns.h"
+#include "policy.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -109,6 +110,7 @@ struct sgw_engine : Plan {   // the plan (plan.h: what make_plan decided) + the 
     uint32_t* d_doffsets = nullptr;
     TurnState* d_turn = nullptr;   // device-side turn state (sgw_turn_*): a whole policy turn as one capturable submission
     bool turn_rows = false;        // sgw_turn_bind gave replay rows
+    int64_t turn_ring_cap[SGW_MAX_AGENTS] = {};   // ... host mirror: rows of agent a's ring, whatever columns it binds (sgw_turn_policy_sample)
     int64_t turn_cap[SGW_MAX_AGENTS] = {};        // ... host mirror: rows of agent a's ring (0: none, or no states)
     int64_t turn_row_bytes[SGW_MAX_AGENTS] = {};  // ... bytes of one of its rows (E * row_elems * element size)
     const void* turn_states[SGW_MAX_AGENTS] = {};
@@ -949,7 +951,7 @@ int sgw_turn_bind(sgw_engine* e, const sgw_turn_rows* rows) {
         h.states[a] = nullptr; h.rewards[a] = nullptr; h.actions[a] = nullptr; h.dones[a] = nullptr;
     }
     e->turn_rows = false;
-    for (int a = 0; a < SGW_MAX_AGENTS; ++a) { e->turn_cap[a] = 0; e->turn_row_bytes[a] = 0; e->turn_states[a] = nullptr; }
+    for (int a = 0; a < SGW_MAX_AGENTS; ++a) { e->turn_cap[a] = 0; e->turn_ring_cap[a] = 0; e->turn_row_bytes[a] = 0; e->turn_states[a] = nullptr; }
     if (rows) {
         for (int a = 0; a < A; ++a) {
             if (rows->capacity[a] <= 0) continue;
@@ -961,6 +963,7 @@ int sgw_turn_bind(sgw_engine* e, const sgw_turn_rows* rows) {
             h.row[a] = rows->row[a]; h.cap[a] = rows->capacity[a]; h.step[a] = rows->step[a]; h.row_elems[a] = rows->row_elems[a];
             h.states[a] = rows->states[a]; h.rewards[a] = rows->rewards[a]; h.actions[a] = rows->actions[a];
             h.dones[a] = rows->states[a] ? rows->dones[a] : nullptr;   // (zeroed by the window copy)
+            e->turn_ring_cap[a] = rows->capacity[a];
             if (rows->states[a]) {
                 e->turn_cap[a] = rows->capacity[a];
                 e->turn_row_bytes[a] = (int64_t)e->cfg.num_envs * rows->row_elems[a] * esz;
@@ -1357,6 +1360,67 @@ int sgw_returns(const sgw_returns_desc* d, void* stream) {
         HIP_TRY(hipGetLastError());
     }
     return SGW_OK;
+}
+
+// ---------------------------------------------------------------- stochastic policies (policy.h)
+static int policy_launch(const sgw_policy_desc* d, const TurnState* ts, const char* who, void* stream) {
+    if (!d->dist || !d->out_actions) return fail(SGW_EINVAL, "%s: dist and out_actions must not be NULL", who);
+    if (d->n < 0) return fail(SGW_EINVAL, "%s: n = %lld", who, (long long)d->n);
+    if (d->num_actions < 1 || d->num_actions > kPolicyMaxActions) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, d->num_actions, kPolicyMaxActions);
+    if (d->num_envs < 1) return fail(SGW_EINVAL, "%s: num_envs = %lld", who, (long long)d->num_envs);
+    if (d->row_stride < d->num_actions) return fail(SGW_EINVAL, "%s: row_stride = %lld is smaller than num_actions = %d", who, (long long)d->row_stride, d->num_actions);
+    if (d->dist_type != SGW_POLICY_F32 && d->dist_type != SGW_POLICY_F64) return fail(SGW_EINVAL, "%s: unknown dist_type %d", who, d->dist_type);
+    if (d->mode != SGW_POLICY_PROBS && d->mode != SGW_POLICY_LOGITS) return fail(SGW_EINVAL, "%s: unknown mode %d", who, d->mode);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
+    if (d->epoch >= (1u << 28)) return fail(SGW_EINVAL, "%s: epoch must be < 2^28", who);
+    if (!d->idx) {      // the agent keys the host can see: agent0 .. agent0 + (n - 1) / num_envs
+        const int64_t last = (int64_t)d->agent0 + (d->n > 0 ? (d->n - 1) / d->num_envs : 0);
+        if (d->agent0 < 0 || last >= SGW_MAX_AGENTS)
+            return fail(SGW_EINVAL, "%s: rows are keyed by agents %d .. %lld, outside [0, %d)", who, d->agent0, (long long)last, SGW_MAX_AGENTS);
+    }
+    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    const bool f64 = d->dist_type == SGW_POLICY_F64;
+    const int64_t esz = f64 ? 8 : 4;
+    if (at(d->dist) & (uintptr_t)(esz - 1)) return fail(SGW_EINVAL, "%s: dist is not aligned to its element type", who);
+    if ((at(d->out_log_probs) | at(d->out_entropy)) & 3) return fail(SGW_EINVAL, "%s: misaligned float32 pointer", who);
+    if ((at(d->out_actions) | at(d->idx)) & 7) return fail(SGW_EINVAL, "%s: misaligned int64 pointer", who);
+    if (d->n > INT64_MAX / 8 / d->row_stride) return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->row_stride);
+    if (d->n == 0) return SGW_OK;
+    PolicyParams p{};
+    p.dist = d->dist; p.idx = d->idx; p.out_actions = d->out_actions; p.out_log_probs = d->out_log_probs; p.out_entropy = d->out_entropy;
+    p.ts = ts;
+    p.n = d->n; p.num_envs = d->num_envs; p.stride = d->row_stride; p.tiles = ceil_div(d->n, kBlock);
+    p.nact = d->num_actions; p.agent0 = d->agent0; p.mode = d->mode;
+    p.seed_lo = (uint32_t)d->seed; p.seed_hi = (uint32_t)(d->seed >> 32); p.first_env = (uint32_t)d->first_env;
+    p.epoch = d->epoch; p.turn = d->turn;
+    // 16 bytes per load where every row starts on a 16-byte boundary and is whole 16-byte pieces (nothing behind a row is read)
+    const bool vec = d->num_actions <= 16 && !(at(d->dist) & 15) && ((d->row_stride * esz) & 15) == 0 && ((d->num_actions * esz) & 15) == 0;
+    const unsigned blocks = (unsigned)std::min<int64_t>(p.tiles, kPolicyMaxBlocks);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (f64) launch_policy<true>(p, vec, blocks, s);
+    else launch_policy<false>(p, vec, blocks, s);
+    HIP_TRY(hipGetLastError());
+    return SGW_OK;
+}
+
+int sgw_policy_sample(const sgw_policy_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_policy_sample: desc is NULL");
+    return policy_launch(d, nullptr, "sgw_policy_sample", stream);
+}
+
+int sgw_turn_policy_sample(sgw_engine* e, int32_t agent, const void* dist, int32_t dist_type, int32_t mode, int64_t* out_actions,
+                           float* log_prob_ring, float* out_entropy, void* stream) {
+    if (!e) return fail(SGW_EINVAL, "sgw_turn_policy_sample: NULL engine");
+    if (agent < 0 || agent >= e->cfg.num_agents) return fail(SGW_EINVAL, "sgw_turn_policy_sample: agent %d out of range", agent);
+    if (log_prob_ring && e->turn_ring_cap[agent] <= 0)
+        return fail(SGW_EINVAL, "sgw_turn_policy_sample: agent %d has no replay rows bound (sgw_turn_bind): which row of the ring the turn fills is unknown", agent);
+    sgw_policy_desc d;
+    memset(&d, 0, sizeof(d));
+    d.dist = dist; d.out_actions = out_actions; d.out_log_probs = log_prob_ring; d.out_entropy = out_entropy;
+    d.n = d.num_envs = e->cfg.num_envs; d.row_stride = d.num_actions = e->cfg.num_actions;
+    d.seed = e->cfg.seed; d.first_env = e->cfg.first_env_id;
+    d.agent0 = agent; d.dist_type = dist_type; d.mode = mode;
+    return policy_launch(&d, e->d_turn, "sgw_turn_policy_sample", stream);
 }
 
 int sgw_choose_actions(sgw_engine* e, const float* values, const int64_t* idx, int64_t n, uint32_t epoch, uint32_t turn, int64_t* out, void* stream) {

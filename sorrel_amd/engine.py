@@ -519,6 +519,90 @@ class GridEngine:
         if rc:
             N.check(rc)
 
+    # ------------------------------------------------------------------ stochastic policies
+    def _policy_dist(self, dist):
+        """(tensor, SGW_POLICY_* dist type, mode) of an ``ActionProbs`` / ``ActionLogits`` -- or of a bare tensor, taken as probabilities."""
+        from sorrel_amd.models.base_model import ActionProbs
+
+        t, logits = (dist.tensor, dist.logits) if isinstance(dist, ActionProbs) else (dist, False)
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype not in (torch.float32, torch.float64) or t.device != self.device \
+                or t.stride(1) != 1 or t.stride(0) < t.shape[1] or not 1 <= t.shape[1] <= N.POLICY_MAX_ACTIONS:
+            got = (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t)
+            raise ValueError(f"a distribution is a float32 / float64 [n, 1..{N.POLICY_MAX_ACTIONS}] tensor on {self.device} whose rows are contiguous (got {got})")
+        return t, (N.POLICY_F64 if t.dtype == torch.float64 else N.POLICY_F32), (N.POLICY_LOGITS if logits else N.POLICY_PROBS)
+
+    def _policy_out(self, t, n, dtype, name):
+        if t is None:
+            return None
+        if not torch.is_tensor(t) or t.dtype != dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements on {self.device}")
+        return t
+
+    def policy_sample(self, dist, agent: int = 0, idx: Optional[torch.Tensor] = None, epoch: Optional[int] = None, turn: Optional[int] = None,
+                      out_actions: Optional[torch.Tensor] = None, out_log_probs: Optional[torch.Tensor] = None,
+                      out_entropy: Optional[torch.Tensor] = None):
+        """``sgw_policy_sample``: one action per row of ``dist`` (``ActionProbs`` / ``ActionLogits``, or a bare tensor of probabilities;
+        ``[n, n_actions]``), its log-probability and the row's entropy -- ``Categorical(...).sample()`` / ``.log_prob()`` / ``.entropy()``
+        with the draw keyed by (seed, env, ``epoch``, ``turn``, agent) instead of consumed from a generator.  Row ``k`` belongs to
+        (env, agent) = ``(k % E, agent + k // E)`` -- one agent's ``[E]`` rows, a shared model's agent-major ``[A * E]`` rows -- or, with
+        ``idx`` (int64 ``[n]``), to ``(idx[k] % E, idx[k] // E)``.  ``epoch`` / ``turn`` default to the engine's (the turn in flight).
+        Returns ``(actions int64 [n], log_probs float32 [n], entropy float32 [n])``; with all three ``out_*`` given the call allocates
+        nothing and does not synchronise.  ``out_log_probs=False`` / ``out_entropy=False``: not wanted (not computed; None is returned)."""
+        t, dtype, mode = self._policy_dist(dist)
+        n = int(t.shape[0])
+        if idx is not None and (not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.device != self.device or idx.numel() != n or not idx.is_contiguous()):
+            raise ValueError(f"idx must be a contiguous int64 tensor of {n} elements on {self.device}")
+        acts = self._policy_out(out_actions, n, torch.int64, "out_actions")
+        lps = None if out_log_probs is False else self._policy_out(out_log_probs, n, torch.float32, "out_log_probs")
+        ents = None if out_entropy is False else self._policy_out(out_entropy, n, torch.float32, "out_entropy")
+        if acts is None:
+            acts = torch.empty((n,), dtype=torch.int64, device=self.device)
+        if lps is None and out_log_probs is not False:
+            lps = torch.empty((n,), dtype=torch.float32, device=self.device)
+        if ents is None and out_entropy is not False:
+            ents = torch.empty((n,), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return acts, lps, ents
+        d = N.SgwPolicyDesc()
+        d.dist, d.idx = t.data_ptr(), (idx.data_ptr() if idx is not None else None)
+        d.out_actions = acts.data_ptr()
+        d.out_log_probs, d.out_entropy = (lps.data_ptr() if lps is not None else None), (ents.data_ptr() if ents is not None else None)
+        d.n, d.num_envs, d.row_stride, d.num_actions = n, self.num_envs, int(t.stride(0)) if n > 1 else int(t.shape[1]), int(t.shape[1])
+        d.seed, d.first_env = int(self.spec.seed) & 0xFFFFFFFFFFFFFFFF, self.first_env_id
+        d.epoch, d.turn = int(self.epoch if epoch is None else epoch), int(self.turn if turn is None else turn)
+        d.agent0, d.dist_type, d.mode = int(agent), dtype, mode
+        with self._on_device():
+            rc = self._lib.sgw_policy_sample(C.byref(d), self._stream())
+        if rc:
+            N.check(rc)
+        return acts, lps, ents
+
+    def turn_policy_sample(self, agent: int, dist, out_actions: torch.Tensor, log_prob_ring: Optional[torch.Tensor] = None,
+                           out_entropy: Optional[torch.Tensor] = None):
+        """``sgw_turn_policy_sample``: agent ``agent``'s ``[E, n_actions]`` distribution sampled under the turn protocol -- epoch, the turn in
+        flight and the row of ``log_prob_ring`` (float32 ``[capacity, E]``: a ``RolloutBuffer``'s ``log_probs``) that receives the
+        log-probabilities are the device's own count, so the call is the same every turn and can be recorded.  ``out_actions`` int64 ``[E]``
+        is what ``turn_act`` then takes."""
+        t, dtype, mode = self._policy_dist(dist)
+        E = self.num_envs
+        if tuple(t.shape) != (E, self.spec.num_actions) or not t.is_contiguous():
+            raise ValueError(f"the distribution of a turn is a contiguous [{E}, {self.spec.num_actions}] tensor; got {tuple(t.shape)}")
+        acts = self._policy_out(out_actions, E, torch.int64, "out_actions")
+        if acts is None:
+            raise ValueError("turn_policy_sample writes its actions to out_actions (a fixed address a recorded turn can replay)")
+        ents = self._policy_out(out_entropy, E, torch.float32, "out_entropy")
+        ring = log_prob_ring
+        if ring is not None and (not torch.is_tensor(ring) or ring.dtype != torch.float32 or ring.device != self.device or ring.dim() != 2
+                                 or ring.shape[1] != E or not ring.is_contiguous()):
+            raise ValueError(f"log_prob_ring must be a contiguous float32 [capacity, {E}] tensor on {self.device}")
+        with self._on_device():
+            rc = self._lib.sgw_turn_policy_sample(self._h, int(agent), t.data_ptr(), dtype, mode, acts.data_ptr(),
+                                                  ring.data_ptr() if ring is not None else None, ents.data_ptr() if ents is not None else None,
+                                                  self._stream())
+        if rc:
+            N.check(rc)
+        return acts
+
     # ------------------------------------------------------------------ speculative policy turns
     def speculation_rows(self, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``[A, E, C*V*V]`` float32, agent-major: the windows the policies read in a speculative turn (``turn_resolve``).  Agents that

@@ -130,6 +130,9 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
         self._turn_capture = False   # the turn protocol with device-side counters is in charge of this turn (recording or warming up)
         self._value_agents = set()   # slots whose get_action returns action values: the act launch takes the argmax / explores (SGW_ACT_QF32)
         self._eps_pushed = {}        # slot -> (engine uid, epsilon) last sent to the device's turn state
+        self._sampling_agents = set()  # slots whose get_action returns a distribution (ActionProbs / ActionLogits): sampled by sgw_policy_sample
+        self._policy_store = {}      # slot -> (engine uid, actions int64 [E], log_probs float32 [E]): where a sampled agent's draw lives from turn to turn
+        self._policy_last = {}       # slot -> (actions, log_probs) of its last draw: what add_memory receives
         self._turn_state_at = {}     # engine uid -> (epoch, turn) the device's turn state was last set for by the eager loop
         self._engine = None
         self._engine_version = -1
@@ -810,11 +813,61 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
         for a, eps in todo.items():
             self._eps_pushed[a] = (eng.uid, eps)
 
+    def _sample_policy(self, a: int, eng, dist, mem=None, row=None) -> torch.Tensor:
+        """An agent's distribution (``ActionProbs`` / ``ActionLogits``, ``[E, n_actions]``) -> its actions, int64 ``[E]`` in storage that
+        persists from turn to turn (a fixed address: the act launch reads it as ``SGW_ACT_I64``, a recorded turn replays it).  The draw is
+        keyed by (seed, env, epoch, turn in flight, agent).  The log-probabilities go straight into ``memory.log_probs[row]`` when the
+        agent's memory is a ``RolloutBuffer`` and the row is known -- ``memory.idx`` in the eager loops, the device's own row count under
+        the turn protocol (``sgw_turn_policy_sample``) -- else into per-agent storage (under a recorded turn: nowhere)."""
+        from sorrel_amd.buffers import RolloutBuffer
+
+        E = self.num_envs
+        t = dist.tensor
+        if tuple(t.shape) != (E, eng.spec.num_actions) or t.device != eng.device:
+            raise ValueError(f"{type(dist).__name__} must hold [{E}, {eng.spec.num_actions}] on {eng.device}; got {tuple(t.shape)} on {t.device}")
+        if not t.is_contiguous():
+            dist = type(dist)(t.contiguous())
+        store = self._policy_store.get(a)
+        if store is None or store[0] != eng.uid:
+            store = self._policy_store[a] = (eng.uid, torch.zeros((E,), dtype=torch.int64, device=eng.device),
+                                             torch.zeros((E,), dtype=torch.float32, device=eng.device))
+        if a not in self._sampling_agents:
+            self._sampling_agents.add(a)
+        acts, lps = store[1], store[2]
+        if mem is None:
+            mem = getattr(self.agents[a].model, "memory", None)
+        rollout = isinstance(mem, RolloutBuffer) and mem.num_envs == E and mem.device == eng.device and mem.log_probs.is_contiguous()
+        if self._turn_capture:
+            eng.turn_policy_sample(a, dist, acts, mem.log_probs if rollout else None)
+        else:
+            if rollout and not mem._deferred:
+                lps = mem.log_probs[mem.idx if row is None else row]
+            eng.policy_sample(dist, agent=a, epoch=self.epoch, turn=self.turn, out_actions=acts, out_log_probs=lps, out_entropy=False)
+        self._policy_last[a] = (acts, lps)
+        return acts
+
+    def _memory_action(self, agent: Agent, action):
+        """What ``add_memory`` receives for what ``get_action`` returned: the sampled ``(actions, log_probs)`` for a ``RolloutBuffer`` and the
+        sampled actions for any other memory (a distribution); the record of what the act took (action values); else the action itself."""
+        from sorrel_amd.buffers import RolloutBuffer
+        from sorrel_amd.models.base_model import ActionProbs
+
+        if isinstance(action, ActionProbs):
+            acts, lps = self._policy_last[agent.slot]
+            return (acts, lps) if isinstance(getattr(agent.model, "memory", None), RolloutBuffer) else acts
+        if torch.is_tensor(action) and action.dim() == 2:
+            return self.actions[:, agent.slot]
+        return action
+
     def _act(self, agent: Agent, action) -> torch.Tensor:
+        from sorrel_amd.models.base_model import ActionProbs
+
         eng = self._ensure_engine()
         a = agent.slot
         if self._mixed:
             eng = self._agent_engine[a]          # the handle compiled from this agent's own action list
+        if isinstance(action, ActionProbs):      # a distribution: sampled first; everything below sees the int64 actions
+            action = self._sample_policy(a, eng, action)
         if not torch.is_tensor(action):
             action = torch.full((self.num_envs,), int(action), dtype=torch.uint8, device=self.world.device)
         values = action.dim() == 2

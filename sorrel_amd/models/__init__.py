@@ -1,3 +1,3 @@
-from sorrel_amd.models.base_model import BaseModel, RandomModel
+from sorrel_amd.models.base_model import ActionLogits, ActionProbs, BaseModel, RandomModel
 
-__all__ = ["BaseModel", "RandomModel"]
+__all__ = ["ActionLogits", "ActionProbs", "BaseModel", "RandomModel"]

@@ -12,6 +12,37 @@ import torch
 from sorrel_amd.buffers import Buffer
 
 
+class ActionProbs:
+    """What a model's ``take_action`` returns to say "sample from this": a floating-point ``[E, n_actions]`` tensor of (unnormalised)
+    action probabilities, as ``Categorical(probs=...)`` takes them (``sorrel/models/pytorch/ppo.py:121-137``).  The engine draws the
+    action with its keyed counter RNG and records the log-probability (``sgw_policy_sample``).  A bare float32 2-D tensor keeps
+    meaning action VALUES (``SGW_ACT_QF32``)."""
+
+    logits = False
+    __slots__ = ("tensor",)
+
+    def __init__(self, tensor):
+        if not torch.is_tensor(tensor):
+            raise TypeError(f"{type(self).__name__} wraps a tensor, not {type(tensor).__name__}")
+        if tensor.dim() != 2:
+            raise ValueError(f"{type(self).__name__} wraps an [E, n_actions] tensor; got shape {tuple(tensor.shape)}")
+        if tensor.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{type(self).__name__} wraps a float32 or float64 tensor, not {tensor.dtype}")
+        if not 1 <= tensor.shape[1] <= 256:
+            raise ValueError(f"{type(self).__name__}: 1..256 actions, not {tensor.shape[1]}")
+        self.tensor = tensor
+
+    def __repr__(self):
+        return f"{type(self).__name__}({tuple(self.tensor.shape)}, {self.tensor.dtype})"
+
+
+class ActionLogits(ActionProbs):
+    """``ActionProbs`` for logits (``Categorical(logits=...)``): weights ``exp(x - max x)``."""
+
+    logits = True
+    __slots__ = ()
+
+
 class BaseModel:
     def __init__(self, input_size, action_space: int, memory_size: int = 0, epsilon: float = 0.0, num_envs: int = 1,
                  device=None):

@@ -174,6 +174,7 @@ class _FastPolicyTurn:
         dev = eng.device
         world = env.world
         edits = world.mutations
+        from sorrel_amd.models.base_model import ActionProbs
         slots = [(m[2], r) for m, r in zip(self.agents, rows_i)]
         with eng._on_device():
             for a, (agent, model, mem, _k) in enumerate(self.agents):
@@ -187,10 +188,14 @@ class _FastPolicyTurn:
                 action = model.take_action(state)
                 if world.mutations != edits:          # the model edited the world: windows are rendered on demand from here on, by the generic hooks
                     reward = env._act(agent, action)
-                    mem.add(state, eng.actions[:, a] if torch.is_tensor(action) and action.dim() == 2 else action, reward, agent.is_done(world))
+                    mem.add(state, env._memory_action(agent, action), reward, agent.is_done(world))
                     for later, _m, _mem, _k in self.agents[a + 1:]:
                         later.transition(world)
                     return
+                if isinstance(action, ActionProbs):
+                    # a distribution: sampled (sgw_policy_sample; the log-probabilities straight into the RolloutBuffer's row i), and the
+                    # int64 actions enter the act launch below as any policy's output does (SGW_ACT_I64)
+                    action = env._sample_policy(a, eng, action, mem, i)
                 values = torch.is_tensor(action) and action.dim() == 2
                 if values and a in env._value_agents and action.dtype == torch.float32 and action.device == dev and action.is_contiguous() \
                         and tuple(action.shape) == (E, self.nact):

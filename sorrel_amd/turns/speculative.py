@@ -46,7 +46,7 @@ class SpeculativeTurns:
             return None
         # (the answer only changes with the engine, the agents' models and their memories: asked every turn, computed once -- with 64 agents
         # the checks below are ~100 us of Python)
-        key = (id(eng), eng.row_tail, self.speculate_turns, self.speculation_cost_model,
+        key = (id(eng), eng.row_tail, self.speculate_turns, self.speculation_cost_model, len(self._sampling_agents),
                tuple((id(a.model), id(getattr(a.model, "memory", None)), type(a)) for a in self.agents))
         cached = self.__dict__.get("_spec_groups")
         if cached is not None and cached[0] == key:
@@ -94,11 +94,17 @@ class SpeculativeTurns:
             return None
         per_env = int(np.prod(eng.spec.obs_shape[1:])) + (eng.row_tail if self._spec_generic else 0)
         groups = []
+        from sorrel_amd.buffers import RolloutBuffer
         for a, agent in enumerate(self.agents):
             model = agent.model
             if not self._standard_hooks(agent) or getattr(model, "device_random", False):
                 return None
             mem = getattr(model, "memory", None)
+            # sampling policies (ActionProbs / ActionLogits; a model may say so up front with ``samples_actions = True``) and memories that
+            # record log-probabilities play the eager loop: a pass would have to sample by row index (sgw_policy_sample's idx form) and
+            # re-fill the log-probability rows of re-evaluated windows -- the keyed draw makes that possible, no loop does it yet
+            if a in self._sampling_agents or getattr(model, "samples_actions", False) or isinstance(mem, RolloutBuffer):
+                return None
             if mem is not None and (not isinstance(mem, Buffer) or mem.n_frames != 1 or mem.extra_data or mem.num_envs != eng.num_envs
                                     or mem.device != eng.device or mem.states[0, 0].numel() != per_env or mem._deferred):
                 return None
@@ -161,6 +167,9 @@ class SpeculativeTurns:
 
         def choose(model, x, idx):
             out = model.take_action(x)
+            if not torch.is_tensor(out):
+                raise TypeError(f"{type(model).__name__}.take_action returned {type(out).__name__} in a speculative turn: sampling policies play the eager "
+                                "loop -- declare it with `samples_actions = True` on the model (or give it a RolloutBuffer) so that the turn is declined up front")
             if out.dim() == 2:                                           # action values: the act launch's choice, exploration included (sgw_choose_actions)
                 self._push_epsilon(eng, range(A))
                 out = eng.choose_actions(out, idx, self.epoch, self.turn)
@@ -247,6 +256,9 @@ class SpeculativeTurns:
         def choose(model, x, idx):
             # idx: which (agent, env) pair each row of x belongs to (agent * E + env; None: the row's own number)
             out = model.take_action(x)
+            if not torch.is_tensor(out):
+                raise TypeError(f"{type(model).__name__}.take_action returned {type(out).__name__} in a speculative turn: sampling policies play the eager "
+                                "loop -- declare it with `samples_actions = True` on the model (or give it a RolloutBuffer) so that the turn is declined up front")
             if out.dim() == 2:
                 # action values: what Agent.transition hands to sgw_act (SGW_ACT_QF32) -- the argmax, or with probability agent.epsilon the
                 # engine's draw for (env, turn, agent) (iqn.py:294-309).  The draw is keyed, so the choice stays a function of the window
