@@ -758,6 +758,60 @@ int sgw_policy_sample(const sgw_policy_desc* desc, void* stream);
 int sgw_turn_policy_sample(sgw_engine* eng, int32_t agent, const void* dist, int32_t dist_type, int32_t mode, int64_t* out_actions,
                            float* log_prob_ring, float* out_entropy, void* stream);
 
+/* ---- PPO's clipped loss and its gradients (sorrel/models/pytorch/ppo.py:259-285: the body of train_step's k_epochs loop between
+ * policy.evaluate's network outputs and optimizer.step -- Categorical(probs), log_prob, entropy, the ratio, the two surrogates, the
+ * MSE, loss.mean() and what autograd hands back at the actor's and the critic's outputs; on the device) ----
+ * One launch reads each of n rows once and writes the loss terms' partial sums and BOTH gradients; a second, small launch merges the
+ * partial sums in a fixed order.  No floating-point atomics: two runs give the same bits.  Row k has num_actions (1..256) numbers x
+ * (float32 or float64: dist_type; probabilities or logits: mode), a value v (value_type), an action a (action_type), the stored
+ * log-probability `old` (float32, what sgw_policy_sample wrote) and a return R (returns_type).  All arithmetic is float64, sequential in
+ * index order, every product rounded before it is added (no fused multiply-add).
+ *   distribution  sgw_policy_sample's, in both modes: w_i = x_i, or exp(x_i - max x) for logits; S = ((w_0 + w_1) + ...); q_i = w_i / S;
+ *                 l_i = log(min(max(q_i, 2^-52), 1 - 2^-52)); u_i = 1 if 2^-52 <= q_i <= 1 - 2^-52, else 0; lp = l_a;
+ *                 H = -((q_0 l_0 + q_1 l_1) + ...).  With unchanged parameters lp reproduces the stored log-probability: the ratio is 1.
+ *   invalid       a row that is invalid for sgw_policy_sample (a negative or NaN weight, S zero or not finite, a NaN or +inf maximum
+ *                 logit) or whose action is outside [0, num_actions): every per-row output of that row is NaN, and so are the means.
+ *                 Other rows are untouched by it.
+ *   loss          r = exp(lp - old); A = R - v; lo = 1 - eps_clip, hi = 1 + eps_clip (computed on the host, in double); s1 = r A;
+ *                 s2 = min(max(r, lo), hi) A; P = -min(s1, s2); d = v - R.  Pm, M and Hm are the means over n of P, d^2 and H;
+ *                 L = Pm + value_coef M - entropy_coef Hm.  The reference's loss.mean() is this with value_coef = 0.5 (its scalar MSE is
+ *                 broadcast over the rows).
+ *   dL/dr         torch's rule, ties included: s1 < s2: gr = A;  s1 > s2: gr = A if lo <= r <= hi, else 0;
+ *                 s1 == s2: gr = A / 2 + (A / 2 if lo <= r <= hi, else 0).  No gradient flows through A (the reference detaches it).
+ *   dL/dx         with c = entropy_coef: gl_i = c q_i, at i = a plus -(gr r); gq_i = (u_i ? gl_i / q_i : 0) + c l_i;
+ *                 t = ((gq_0 q_0 + gq_1 q_1) + ...);  probabilities: dL/dx_j = ((gq_j - t) / S) / n;  logits: dL/dx_j = (q_j (gq_j - t)) / n.
+ *   dL/dv         ((2 value_coef) (v - R)) / n.
+ * float32 outputs are the float64 value rounded once.  out_grad_dist has the type and the row stride of dist (what lies between rows is
+ * not written), out_grad_values the type of values; both and out_row_terms are optional (NULL).  The gradients depend on n alone, not on
+ * the sums: they are final after the first launch.  workspace: sgw_ppo_loss_workspace_bytes(n) bytes, 8-byte aligned, overwritten.
+ * Needs no engine; all pointers are device pointers.  Asynchronous on `stream`; everything the host can see -- a NULL required pointer,
+ * an unknown dist_type / mode / value_type / action_type / returns_type, n < 0, num_actions outside 1..256, row_stride < num_actions, a
+ * negative or non-finite eps_clip, a pointer not aligned to its element type, a workspace that is too small, a non-zero reserved field,
+ * n * row_stride beyond 64-bit offsets -- is SGW_EINVAL with the reason in sgw_last_error(), before anything is launched.  n == 0
+ * launches nothing and writes nothing. */
+#define SGW_PPO_ACT_I64 0        /* action_type: int64 actions (a Buffer's) */
+#define SGW_PPO_ACT_U8 1         /* ... uint8 (a TurnBuffer's) */
+typedef struct sgw_ppo_loss_desc {
+    const void* dist;            /* [n] rows of num_actions elements of dist_type (SGW_POLICY_F32 / _F64), row_stride elements apart */
+    const void* values;          /* [n] of value_type (SGW_POLICY_F32 / _F64) */
+    const void* actions;         /* [n] of action_type */
+    const float* old_log_probs;  /* [n] */
+    const void* returns;         /* [n] of returns_type (SGW_POLICY_F32 / _F64) */
+    void* out_grad_dist;         /* dL/dx, laid out as dist, or NULL */
+    void* out_grad_values;       /* dL/dv [n] of value_type, or NULL */
+    double* out_row_terms;       /* [n][3] = (P, d^2, H) of every row, or NULL */
+    double* out_terms;           /* [4] = L, Pm, M, Hm */
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t n, row_stride;
+    double eps_clip, entropy_coef, value_coef;
+    int32_t num_actions, dist_type, mode, value_type, action_type, returns_type;
+    int32_t reserved0, reserved1;    /* reserved: 0 */
+} sgw_ppo_loss_desc;
+int sgw_ppo_loss(const sgw_ppo_loss_desc* desc, void* stream);
+/* Bytes of workspace a call over n rows needs (0 for no rows); a negative code for n < 0. */
+int64_t sgw_ppo_loss_workspace_bytes(int64_t n);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

@@ -35,6 +35,7 @@ STREAM_POLICY = 10          # sgw_policy_sample's draw: index = agent, turn = th
 POLICY_F32, POLICY_F64 = 0, 1
 POLICY_PROBS, POLICY_LOGITS = 0, 1
 POLICY_MAX_ACTIONS = 256
+PPO_ACT_I64, PPO_ACT_U8 = 0, 1
 POLICY_INVALID_ACTION = 255  # the action of a row torch's Categorical would raise for (its log-probability and entropy are NaN)
 
 
@@ -174,6 +175,22 @@ class SgwPolicyDesc(C.Structure):
     ]
 
 
+class SgwPpoLossDesc(C.Structure):
+    """Mirror of ``struct sgw_ppo_loss_desc`` (include/sgw.h): one ``sgw_ppo_loss`` call; layout checked by tests/test_ppo_loss_cpu.py."""
+
+    _fields_ = [
+        ("dist", C.c_void_p), ("values", C.c_void_p), ("actions", C.c_void_p), ("old_log_probs", C.c_void_p), ("returns", C.c_void_p),
+        ("out_grad_dist", C.c_void_p), ("out_grad_values", C.c_void_p), ("out_row_terms", C.c_void_p), ("out_terms", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("n", C.c_int64), ("row_stride", C.c_int64),
+        ("eps_clip", C.c_double), ("entropy_coef", C.c_double), ("value_coef", C.c_double),
+        ("num_actions", C.c_int32), ("dist_type", C.c_int32), ("mode", C.c_int32), ("value_type", C.c_int32), ("action_type", C.c_int32),
+        ("returns_type", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -187,6 +204,7 @@ EXPORTS = (
     "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render", "sgw_sample",
     "sgw_returns", "sgw_returns_workspace_bytes",
     "sgw_policy_sample", "sgw_turn_policy_sample",
+    "sgw_ppo_loss", "sgw_ppo_loss_workspace_bytes",
     "sgw_last_error", "sgw_version",
 )
 
@@ -336,6 +354,10 @@ def load():
     lib.sgw_policy_sample.restype = C.c_int
     lib.sgw_turn_policy_sample.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.sgw_turn_policy_sample.restype = C.c_int
+    lib.sgw_ppo_loss.argtypes = [C.POINTER(SgwPpoLossDesc), vp]
+    lib.sgw_ppo_loss.restype = C.c_int
+    lib.sgw_ppo_loss_workspace_bytes.argtypes = [C.c_int64]
+    lib.sgw_ppo_loss_workspace_bytes.restype = C.c_int64
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

@@ -72,6 +72,7 @@ namespace {
 #include "sample.h"
 #include "returns.h"
 #include "policy.h"
+#include "ppo_loss.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -1421,6 +1422,62 @@ int sgw_turn_policy_sample(sgw_engine* e, int32_t agent, const void* dist, int32
     d.seed = e->cfg.seed; d.first_env = e->cfg.first_env_id;
     d.agent0 = agent; d.dist_type = dist_type; d.mode = mode;
     return policy_launch(&d, e->d_turn, "sgw_turn_policy_sample", stream);
+}
+
+// ---------------------------------------------------------------- PPO's clipped loss (ppo_loss.h)
+int64_t sgw_ppo_loss_workspace_bytes(int64_t n) {
+    if (n < 0 || n > INT64_MAX / 32) return fail(SGW_EINVAL, "sgw_ppo_loss_workspace_bytes: n = %lld outside [0, 2^58)", (long long)n);
+    return ppo_loss_blocks(n) * 3 * (int64_t)sizeof(double);
+}
+
+int sgw_ppo_loss(const sgw_ppo_loss_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_ppo_loss: desc is NULL");
+    if (!d->dist || !d->values || !d->actions || !d->old_log_probs || !d->returns || !d->out_terms)
+        return fail(SGW_EINVAL, "sgw_ppo_loss: dist, values, actions, old_log_probs, returns and out_terms must not be NULL");
+    if (d->n < 0) return fail(SGW_EINVAL, "sgw_ppo_loss: n = %lld", (long long)d->n);
+    if (d->num_actions < 1 || d->num_actions > kPpoMaxActions) return fail(SGW_EINVAL, "sgw_ppo_loss: num_actions = %d outside [1, %d]", d->num_actions, kPpoMaxActions);
+    if (d->row_stride < d->num_actions) return fail(SGW_EINVAL, "sgw_ppo_loss: row_stride = %lld is smaller than num_actions = %d", (long long)d->row_stride, d->num_actions);
+    auto is_float = [](int32_t t) { return t == SGW_POLICY_F32 || t == SGW_POLICY_F64; };
+    if (!is_float(d->dist_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown dist_type %d", d->dist_type);
+    if (d->mode != SGW_POLICY_PROBS && d->mode != SGW_POLICY_LOGITS) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown mode %d", d->mode);
+    if (!is_float(d->value_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown value_type %d", d->value_type);
+    if (d->action_type != SGW_PPO_ACT_I64 && d->action_type != SGW_PPO_ACT_U8) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown action_type %d", d->action_type);
+    if (!is_float(d->returns_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown returns_type %d", d->returns_type);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "sgw_ppo_loss: reserved fields must be 0");
+    if (!(d->eps_clip >= 0.0) || !std::isfinite(d->eps_clip)) return fail(SGW_EINVAL, "sgw_ppo_loss: eps_clip = %g must be finite and not negative", d->eps_clip);
+    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    auto mask = [](int32_t t) { return (uintptr_t)(t == SGW_POLICY_F64 ? 7 : 3); };
+    if ((at(d->dist) | at(d->out_grad_dist)) & mask(d->dist_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: dist / out_grad_dist is not aligned to its element type");
+    if ((at(d->values) | at(d->out_grad_values)) & mask(d->value_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: values / out_grad_values is not aligned to its element type");
+    if (at(d->returns) & mask(d->returns_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: returns is not aligned to its element type");
+    if (at(d->old_log_probs) & 3) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned float32 pointer (old_log_probs)");
+    if (d->action_type == SGW_PPO_ACT_I64 && (at(d->actions) & 7)) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned int64 pointer (actions)");
+    if ((at(d->out_row_terms) | at(d->out_terms) | at(d->workspace)) & 7) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned float64 pointer (out_row_terms, out_terms or workspace)");
+    if (d->n > INT64_MAX / 8 / d->row_stride || d->n > INT64_MAX / 32) return fail(SGW_EINVAL, "sgw_ppo_loss: n = %lld rows of stride %lld do not fit 64-bit offsets", (long long)d->n, (long long)d->row_stride);
+    const unsigned blocks = (unsigned)ppo_loss_blocks(d->n);
+    const int64_t need = (int64_t)blocks * 3 * (int64_t)sizeof(double);
+    if (need > 0 && (!d->workspace || d->workspace_bytes < need))
+        return fail(SGW_EINVAL, "sgw_ppo_loss: needs a workspace of %lld bytes (sgw_ppo_loss_workspace_bytes); got %lld", (long long)need, d->workspace ? (long long)d->workspace_bytes : 0ll);
+    if (d->n == 0) return SGW_OK;
+    PpoLossParams p{};
+    p.dist = d->dist; p.values = d->values; p.actions = d->actions; p.old_lp = d->old_log_probs; p.returns = d->returns;
+    p.g_dist = d->out_grad_dist; p.g_values = d->out_grad_values; p.row_terms = d->out_row_terms; p.out_terms = d->out_terms;
+    p.partials = static_cast<double*>(d->workspace);
+    p.n = d->n; p.stride = d->row_stride; p.tiles = ceil_div(d->n, kBlock);
+    p.lo = 1.0 - d->eps_clip; p.hi = 1.0 + d->eps_clip; p.c = d->entropy_coef; p.vc = d->value_coef;
+    p.nact = d->num_actions; p.mode = d->mode; p.vtype = d->value_type; p.atype = d->action_type; p.rtype = d->returns_type;
+    p.nparts = (int32_t)blocks;
+    const bool f64 = d->dist_type == SGW_POLICY_F64;
+    const int64_t esz = f64 ? 8 : 4;
+    // 16 bytes per access where every row of dist AND of its gradient starts on a 16-byte boundary and is whole 16-byte pieces
+    const bool vec = d->num_actions <= 16 && !((at(d->dist) | at(d->out_grad_dist)) & 15) && ((d->row_stride * esz) & 15) == 0 && ((d->num_actions * esz) & 15) == 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (f64) launch_ppo_loss<true>(p, vec, blocks, s);
+    else launch_ppo_loss<false>(p, vec, blocks, s);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ppo_loss_merge_kernel, dim3(1), dim3(kBlock), 0, s, p);
+    HIP_TRY(hipGetLastError());
+    return SGW_OK;
 }
 
 int sgw_choose_actions(sgw_engine* e, const float* values, const int64_t* idx, int64_t n, uint32_t epoch, uint32_t turn, int64_t* out, void* stream) {

@@ -1,0 +1,194 @@
+"""PPO's clipped loss on the device (``sorrel/models/pytorch/ppo.py:259-285``: the body of ``PyTorchPPO.train_step``'s ``k_epochs`` loop
+between the networks' outputs and ``optimizer.step``).
+
+``ppo_loss_terms`` is one ``sgw_ppo_loss`` call (``sorrel_amd/csrc/ppo_loss.h``): it reads each row once and writes the loss terms and
+the gradients of the mean loss at the actor's and the critic's outputs.  ``ppo_loss`` wraps it as a ``torch.autograd.Function`` whose
+``backward`` hands those gradients on, so a user's learner writes::
+
+    loss = ppo_loss(ActionProbs(actor(states)), critic(states).squeeze(-1), actions, old_log_probs, returns, eps_clip, entropy_coef)
+    optimizer.zero_grad(); loss.backward(); optimizer.step()
+
+``_ppo_loss_torch`` is the reference's lines restated with torch ops: the path of CPU tensors, and what the kernel is compared with and
+timed against.  Device tensors always use the kernel.  The networks, the optimiser and the learner class stay the user's."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from sorrel_amd.models.base_model import ActionProbs
+
+_FLOATS = (torch.float32, torch.float64)
+
+
+class PPOLoss:
+    """What ``ppo_loss_terms`` gives back: ``loss`` = ``policy + value_coef * value - entropy_coef * entropy``, the three means (0-d
+    float64 tensors, views of ``terms`` = ``[L, Pm, M, Hm]``), ``grad_dist`` (dL/d dist: the shape, dtype and strides of the
+    distribution's tensor) and ``grad_values`` (dL/d values), and ``row_terms`` (float64 ``[n, 3]`` = per-row policy term, squared
+    error and entropy) if asked for, else None.  Passed back as ``out=`` its tensors are overwritten in place."""
+
+    __slots__ = ("terms", "loss", "policy", "value", "entropy", "grad_dist", "grad_values", "row_terms", "_workspace")
+
+    def __init__(self, dist, values, row_terms=False):
+        dev, n = dist.device, int(dist.shape[0])
+        self.terms = torch.empty((4,), dtype=torch.float64, device=dev)
+        self.loss, self.policy, self.value, self.entropy = self.terms[0], self.terms[1], self.terms[2], self.terms[3]
+        self.grad_dist = torch.empty_strided(dist.shape, dist.stride(), dtype=dist.dtype, device=dev)
+        self.grad_values = torch.empty(values.shape, dtype=values.dtype, device=dev)
+        self.row_terms = torch.empty((n, 3), dtype=torch.float64, device=dev) if row_terms else None
+        self._workspace = None
+        if dev.type == "cuda":
+            from sorrel_amd import _native as N
+
+            need = int(N.load().sgw_ppo_loss_workspace_bytes(n))
+            self._workspace = torch.empty((max(need, 8) // 8,), dtype=torch.float64, device=dev)
+
+    def __repr__(self):
+        return f"PPOLoss(n={self.grad_values.numel()}, num_actions={self.grad_dist.shape[1]})"
+
+
+def _unwrap(dist):
+    """``(tensor, logits)`` of an ``ActionProbs`` / ``ActionLogits``, or of a bare 2-D tensor taken as probabilities."""
+    if isinstance(dist, ActionProbs):
+        return dist.tensor, bool(dist.logits)
+    return ActionProbs(dist).tensor, False
+
+
+def _check(t, values, actions, old_log_probs, returns):
+    n, na = int(t.shape[0]), int(t.shape[1])
+    if t.stride(1) != 1 and na > 1 or (n > 1 and t.stride(0) < na):
+        raise ValueError(f"the distribution's rows must be contiguous (strides {tuple(t.stride())})")
+    for name, x, dtypes in (("values", values, _FLOATS), ("actions", actions, (torch.int64, torch.uint8)),
+                            ("old_log_probs", old_log_probs, (torch.float32,)), ("returns", returns, _FLOATS)):
+        if not torch.is_tensor(x):
+            raise TypeError(f"{name} must be a tensor, not {type(x).__name__}")
+        if x.dtype not in dtypes:
+            raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, not {x.dtype}")
+        if x.numel() != n:
+            raise ValueError(f"{name} has {x.numel()} elements for {n} rows of the distribution")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if x.device != t.device:
+            raise ValueError(f"{name} is on {x.device}, the distribution on {t.device}")
+    return n, na
+
+
+def _check_out(out, t, values, row_terms):
+    if not isinstance(out, PPOLoss):
+        raise TypeError("out= takes an earlier PPOLoss")
+    n = int(t.shape[0])
+    tensors = [out.terms, out.grad_dist, out.grad_values] + [x for x in (out.row_terms, out._workspace) if x is not None]
+    if (out.grad_dist.shape != t.shape or out.grad_dist.stride() != t.stride() or out.grad_dist.dtype != t.dtype
+            or out.grad_values.shape != values.shape or out.grad_values.dtype != values.dtype
+            or any(x.device != t.device for x in tensors)
+            or (row_terms and (out.row_terms is None or tuple(out.row_terms.shape) != (n, 3)))
+            or (t.device.type == "cuda" and out._workspace is None)):
+        raise ValueError("out= was made for other shapes, strides, dtypes or another device")
+    return out
+
+
+def _ppo_loss_torch(t, logits, values, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef=0.5):
+    """The reference's lines (``ppo.py:152-158`` and ``:265-284``) with torch ops, in float64 as its ``ActorCritic`` runs: returns
+    ``(loss.mean(), policy_loss.mean(), critic_loss, dist_entropy.mean(), policy_loss, squared errors, dist_entropy)``, connected to
+    ``t`` and ``values`` for autograd.  ``Categorical`` skips its argument check (a host synchronisation the timed baseline is
+    spared), so an invalid row is not refused here."""
+    from torch.distributions import Categorical
+
+    n = t.shape[0]
+    x = t.double()
+    dist = Categorical(logits=x, validate_args=False) if logits else Categorical(probs=x, validate_args=False)
+    acts = actions.reshape(n).long()
+    log_probs = dist.log_prob(acts)
+    dist_entropy = dist.entropy()
+    state_values = values.reshape(n).double()
+    rewards = returns.reshape(n).double()
+    ratios = torch.exp(log_probs - old_log_probs.reshape(n).double().detach())
+    advantages = rewards - state_values.detach()
+    surr1 = ratios * advantages
+    surr2 = torch.clamp(ratios, 1 - eps_clip, 1 + eps_clip) * advantages
+    sq = (state_values - rewards) ** 2
+    critic_loss = sq.mean()                                 # nn.MSELoss()(state_values, rewards)
+    policy_loss = -torch.min(surr1, surr2)
+    loss = policy_loss + value_coef * critic_loss - entropy_coef * dist_entropy
+    return loss.mean(), policy_loss.mean(), critic_loss, dist_entropy.mean(), policy_loss, sq, dist_entropy
+
+
+def _terms_by_torch(t, logits, values, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef, res):
+    with torch.enable_grad():
+        leaf_t, leaf_v = t.detach().requires_grad_(True), values.detach().requires_grad_(True)
+        L, Pm, M, Hm, P, sq, H = _ppo_loss_torch(leaf_t, logits, leaf_v, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef)
+        g_t, g_v = torch.autograd.grad(L, (leaf_t, leaf_v))
+    res.terms.copy_(torch.stack((L, Pm, M, Hm)).detach())
+    res.grad_dist.copy_(g_t)
+    res.grad_values.copy_(g_v)
+    if res.row_terms is not None:
+        res.row_terms.copy_(torch.stack((P, sq, H), dim=1).detach())
+    return res
+
+
+def ppo_loss_terms(dist, values, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef=0.5, *, out=None, row_terms=False):
+    """The clipped PPO loss of ``n`` rows and its gradients: ``dist`` is an ``ActionProbs`` / ``ActionLogits`` or a bare ``[n, n_actions]``
+    tensor of (unnormalised) probabilities, float32 or float64; ``values`` (float32 / float64), ``actions`` (int64 / uint8),
+    ``old_log_probs`` (float32: what ``sgw_policy_sample`` stored) and ``returns`` (float32 / float64: ``Returns.normalized`` or
+    ``.returns``) have any leading shape with ``n`` elements -- a ring segment ``[count, E]`` with ``dist`` its ``[count * E, A]`` view --
+    and are contiguous.  Returns a ``PPOLoss``.  On a HIP device this is one ``sgw_ppo_loss`` call in float64 whatever the inputs'
+    types; with ``out=`` (an earlier result for the same shapes) it allocates nothing and does not synchronise, so it can be recorded
+    into a graph.  A row ``Categorical`` would refuse, or whose action is out of range, gives NaN for its outputs and for the means."""
+    t, logits = _unwrap(dist)
+    if not torch.is_tensor(values):
+        raise TypeError(f"values must be a tensor, not {type(values).__name__}")
+    n, na = _check(t, values, actions, old_log_probs, returns)
+    eps_clip, entropy_coef, value_coef = float(eps_clip), float(entropy_coef), float(value_coef)
+    if not (eps_clip >= 0.0 and eps_clip != float("inf")):
+        raise ValueError(f"eps_clip = {eps_clip} must be finite and not negative")
+    res = PPOLoss(t, values, row_terms) if out is None else _check_out(out, t, values, row_terms)
+    if t.device.type != "cuda":
+        return _terms_by_torch(t, logits, values, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef, res)
+    if n == 0:
+        res.terms.fill_(float("nan"))                        # the mean of nothing, as torch's
+        return res
+    from sorrel_amd import _native as N
+
+    d = N.SgwPpoLossDesc()
+    d.dist, d.values, d.actions, d.old_log_probs, d.returns = t.data_ptr(), values.data_ptr(), actions.data_ptr(), old_log_probs.data_ptr(), returns.data_ptr()
+    d.out_grad_dist, d.out_grad_values, d.out_terms = res.grad_dist.data_ptr(), res.grad_values.data_ptr(), res.terms.data_ptr()
+    if row_terms:
+        d.out_row_terms = res.row_terms.data_ptr()
+    d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
+    d.n, d.row_stride, d.num_actions = n, (int(t.stride(0)) if n > 1 else na), na
+    d.eps_clip, d.entropy_coef, d.value_coef = eps_clip, entropy_coef, value_coef
+    f = {torch.float32: N.POLICY_F32, torch.float64: N.POLICY_F64}
+    d.dist_type, d.mode = f[t.dtype], (N.POLICY_LOGITS if logits else N.POLICY_PROBS)
+    d.value_type, d.returns_type = f[values.dtype], f[returns.dtype]
+    d.action_type = N.PPO_ACT_U8 if actions.dtype == torch.uint8 else N.PPO_ACT_I64
+    with torch.cuda.device(t.device):
+        N.check(N.load().sgw_ppo_loss(C.byref(d), C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
+    return res
+
+
+class _PPOLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, values, logits, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef, out):
+        from sorrel_amd.models.base_model import ActionLogits
+
+        res = ppo_loss_terms((ActionLogits if logits else ActionProbs)(t.detach()), values.detach(), actions, old_log_probs, returns,
+                             eps_clip, entropy_coef, value_coef, out=out)
+        ctx.save_for_backward(res.grad_dist, res.grad_values)
+        return res.loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_t, g_v = ctx.saved_tensors
+        # one multiply per gradient: the incoming gradient is a device scalar (1 after loss.backward()) and is not read on the host
+        return (g_t * grad_out.to(g_t.dtype) if ctx.needs_input_grad[0] else None, g_v * grad_out.to(g_v.dtype) if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None, None, None)
+
+
+def ppo_loss(dist, values, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef=0.5, *, out=None):
+    """``ppo_loss_terms`` as a differentiable scalar: the loss ``L`` (0-d float64), connected to the distribution's tensor and to
+    ``values``.  The forward launch has already written both gradients; ``backward`` multiplies them by the incoming gradient and hands
+    them on to the networks.  ``out=``: a ``PPOLoss`` to reuse (it must not be overwritten before ``backward`` ran)."""
+    t, logits = _unwrap(dist)
+    if not torch.is_tensor(values):
+        raise TypeError(f"values must be a tensor, not {type(values).__name__}")
+    return _PPOLossFn.apply(t, values, logits, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef, out)
