@@ -812,6 +812,64 @@ int sgw_ppo_loss(const sgw_ppo_loss_desc* desc, void* stream);
 /* Bytes of workspace a call over n rows needs (0 for no rows); a negative code for n < 0. */
 int64_t sgw_ppo_loss_workspace_bytes(int64_t n);
 
+/* ---- IQN's quantile Huber loss and its gradient (sorrel/models/pytorch/iqn.py:359-405 and calculate_huber_loss, :451-464: the body of
+ * iRainbowModel.train_step between the three network outputs and loss.backward() -- the double-DQN action choice, the two gathers, the
+ * n-step target, the [B][N][N] pairwise TD tensor, the Huber `where`, the `valid` mask, the quantile weights, the mean, and what autograd
+ * hands back at the local net's output; on the device) ----
+ * One launch reads every row once and writes the gradient and per-workgroup sums; a second, small launch merges the sums in a fixed
+ * order.  No floating-point atomics: two runs give the same bits.  Batch row b of n has num_quantiles = N (1..64) quantiles of
+ * num_actions = A (1..256) actions in each of three contiguous float32 [n][N][A] tensors: q_next_local (the local net on the next
+ * states: it only chooses the action), q_next_target (the target net on the next states) and q_expected (the local net on the states:
+ * the only tensor with a gradient); taus float32 [n][N] (the taus of the q_expected call); an action (action_type), a reward and a done
+ * flag (float32) and a row weight `valid` (valid_type; any weight, not only 0 / 1).  discount = GAMMA ** n_step, computed by the caller.
+ * float32 arithmetic is torch's on the CPU, every product rounded before it is added (no fused multiply-add).
+ *   action      m_a = (((q_next_local[b][0][a] + q_next_local[b][1][a]) + ...)) / (float)N, summed serially over the quantiles in float32;
+ *               a* = the first maximum of m, a NaN counting as a maximum (SGW_ACT_QF32's rule)
+ *   target      T_j = rewards_b + (((float)discount * q_next_target[b][j][a*]) * (1.0f - dones_b));  X_i = q_expected[b][i][actions_b];
+ *               td_ij = T_j - X_i  (the target's index is the LAST axis; tau_i belongs to X_i)
+ *   Huber       kappa = 1:  h_ij = |td_ij| <= 1 ? 0.5f * (td_ij * td_ij) : |td_ij| - 0.5f;  w_ij = |tau_i - (td_ij < 0 ? 1.0f : 0.0f)|
+ *   loss        float64 from here on (where the reference's float64 `valid` promotes it): ql_ij = (double)w_ij * ((double)h_ij *
+ *               (double)valid_b);  S_b = the serial sum of ql_ij over j for each i, then of those N sums over i, in index order;
+ *               L = (the sum of S_b over b) / (n N N).  The S_b are added in an order that depends on indices alone.
+ *   gradient    g_ij = (float)(((1.0 / (n N N)) * (double)w_ij) * (double)valid_b);  e_ij = |td_ij| <= 1 ? g_ij * td_ij : g_ij * s_ij
+ *               with s_ij = (td_ij > 0) - (td_ij < 0), in float32;  dL/dq_expected[b][i][actions_b] = (float)(-(the serial float64 sum
+ *               over j of (double)e_ij)).  Every other element of row b is an exact +0: the WHOLE [n][N][A] gradient is written, no
+ *               memset precedes the call.  Nothing flows to q_next_local, q_next_target or taus.
+ *   invalid     a row whose action is outside [0, A): X_i is NaN, so its td_error is NaN; S_b and its whole gradient row are NaN, and
+ *               so is L.  Its a* and every other row are untouched by it.  Non-finite inputs give what IEEE arithmetic gives.
+ * out_grad_expected, out_next_actions, out_row_terms and out_td_error are optional (NULL).  workspace:
+ * sgw_iqn_loss_workspace_bytes(n, num_quantiles) bytes, 8-byte aligned, overwritten.  Needs no engine; all pointers are device pointers.
+ * Asynchronous on `stream`; everything the host can see -- a NULL required pointer, an unknown action_type / valid_type, n < 0,
+ * num_quantiles outside 1..64, num_actions outside 1..256, a discount that is not finite, a pointer not aligned to its element type, a
+ * missing or short workspace, a non-zero reserved field, n * N * max(A, N) beyond 64-bit offsets -- is SGW_EINVAL with the reason in
+ * sgw_last_error(), before anything is launched.  n == 0 launches nothing and writes nothing. */
+#define SGW_IQN_MAX_QUANTILES 64
+typedef struct sgw_iqn_loss_desc {
+    const float* q_next_local;   /* [n][N][A] */
+    const float* q_next_target;  /* [n][N][A] */
+    const float* q_expected;     /* [n][N][A] */
+    const float* taus;           /* [n][N] */
+    const void* actions;         /* [n] of action_type (SGW_PPO_ACT_I64 / _U8) */
+    const float* rewards;        /* [n] */
+    const float* dones;          /* [n] */
+    const void* valid;           /* [n] of valid_type (SGW_POLICY_F32 / _F64) */
+    double* out_terms;           /* [1] = L */
+    float* out_grad_expected;    /* dL/dq_expected [n][N][A], or NULL */
+    int64_t* out_next_actions;   /* [n] = a*, or NULL */
+    double* out_row_terms;       /* [n] = S_b, or NULL */
+    float* out_td_error;         /* [n][N][N] = td_ij, or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t n;
+    double discount;
+    int32_t num_quantiles, num_actions, action_type, valid_type;
+    int32_t reserved0, reserved1;    /* reserved: 0 */
+} sgw_iqn_loss_desc;
+int sgw_iqn_loss(const sgw_iqn_loss_desc* desc, void* stream);
+/* Bytes of workspace a call over n rows of num_quantiles quantiles needs (0 for no rows); a negative code for n < 0 or num_quantiles
+ * outside 1..64. */
+int64_t sgw_iqn_loss_workspace_bytes(int64_t n, int32_t num_quantiles);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

@@ -36,6 +36,7 @@ POLICY_F32, POLICY_F64 = 0, 1
 POLICY_PROBS, POLICY_LOGITS = 0, 1
 POLICY_MAX_ACTIONS = 256
 PPO_ACT_I64, PPO_ACT_U8 = 0, 1
+IQN_MAX_QUANTILES = 64
 POLICY_INVALID_ACTION = 255  # the action of a row torch's Categorical would raise for (its log-probability and entropy are NaN)
 
 
@@ -191,6 +192,23 @@ class SgwPpoLossDesc(C.Structure):
     ]
 
 
+class SgwIqnLossDesc(C.Structure):
+    """Mirror of ``struct sgw_iqn_loss_desc`` (include/sgw.h): one ``sgw_iqn_loss`` call; layout checked by tests/test_iqn_loss_cpu.py."""
+
+    _fields_ = [
+        ("q_next_local", C.c_void_p), ("q_next_target", C.c_void_p), ("q_expected", C.c_void_p), ("taus", C.c_void_p),
+        ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("valid", C.c_void_p),
+        ("out_terms", C.c_void_p), ("out_grad_expected", C.c_void_p), ("out_next_actions", C.c_void_p), ("out_row_terms", C.c_void_p),
+        ("out_td_error", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("n", C.c_int64),
+        ("discount", C.c_double),
+        ("num_quantiles", C.c_int32), ("num_actions", C.c_int32), ("action_type", C.c_int32), ("valid_type", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -205,6 +223,7 @@ EXPORTS = (
     "sgw_returns", "sgw_returns_workspace_bytes",
     "sgw_policy_sample", "sgw_turn_policy_sample",
     "sgw_ppo_loss", "sgw_ppo_loss_workspace_bytes",
+    "sgw_iqn_loss", "sgw_iqn_loss_workspace_bytes",
     "sgw_last_error", "sgw_version",
 )
 
@@ -358,6 +377,10 @@ def load():
     lib.sgw_ppo_loss.restype = C.c_int
     lib.sgw_ppo_loss_workspace_bytes.argtypes = [C.c_int64]
     lib.sgw_ppo_loss_workspace_bytes.restype = C.c_int64
+    lib.sgw_iqn_loss.argtypes = [C.POINTER(SgwIqnLossDesc), vp]
+    lib.sgw_iqn_loss.restype = C.c_int
+    lib.sgw_iqn_loss_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.sgw_iqn_loss_workspace_bytes.restype = C.c_int64
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

@@ -73,6 +73,7 @@ namespace {
 #include "returns.h"
 #include "policy.h"
 #include "ppo_loss.h"
+#include "iqn_loss.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -1476,6 +1477,59 @@ int sgw_ppo_loss(const sgw_ppo_loss_desc* d, void* stream) {
     else launch_ppo_loss<false>(p, vec, blocks, s);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(ppo_loss_merge_kernel, dim3(1), dim3(kBlock), 0, s, p);
+    HIP_TRY(hipGetLastError());
+    return SGW_OK;
+}
+
+// ---------------------------------------------------------------- IQN's quantile Huber loss (iqn_loss.h)
+int64_t sgw_iqn_loss_workspace_bytes(int64_t n, int32_t num_quantiles) {
+    if (n < 0 || n > INT64_MAX / 32) return fail(SGW_EINVAL, "sgw_iqn_loss_workspace_bytes: n = %lld outside [0, 2^58)", (long long)n);
+    if (num_quantiles < 1 || num_quantiles > kIqnMaxQuantiles) return fail(SGW_EINVAL, "sgw_iqn_loss_workspace_bytes: num_quantiles = %d outside [1, %d]", num_quantiles, kIqnMaxQuantiles);
+    return iqn_loss_blocks(n, num_quantiles) * (int64_t)sizeof(double);
+}
+
+int sgw_iqn_loss(const sgw_iqn_loss_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_iqn_loss: desc is NULL");
+    if (!d->q_next_local || !d->q_next_target || !d->q_expected || !d->taus || !d->actions || !d->rewards || !d->dones || !d->valid || !d->out_terms)
+        return fail(SGW_EINVAL, "sgw_iqn_loss: q_next_local, q_next_target, q_expected, taus, actions, rewards, dones, valid and out_terms must not be NULL");
+    if (d->n < 0) return fail(SGW_EINVAL, "sgw_iqn_loss: n = %lld", (long long)d->n);
+    if (d->num_quantiles < 1 || d->num_quantiles > kIqnMaxQuantiles) return fail(SGW_EINVAL, "sgw_iqn_loss: num_quantiles = %d outside [1, %d]", d->num_quantiles, kIqnMaxQuantiles);
+    if (d->num_actions < 1 || d->num_actions > kIqnMaxActions) return fail(SGW_EINVAL, "sgw_iqn_loss: num_actions = %d outside [1, %d]", d->num_actions, kIqnMaxActions);
+    if (d->action_type != SGW_PPO_ACT_I64 && d->action_type != SGW_PPO_ACT_U8) return fail(SGW_EINVAL, "sgw_iqn_loss: unknown action_type %d", d->action_type);
+    if (d->valid_type != SGW_POLICY_F32 && d->valid_type != SGW_POLICY_F64) return fail(SGW_EINVAL, "sgw_iqn_loss: unknown valid_type %d", d->valid_type);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "sgw_iqn_loss: reserved fields must be 0");
+    if (!std::isfinite(d->discount)) return fail(SGW_EINVAL, "sgw_iqn_loss: discount = %g must be finite", d->discount);
+    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    if ((at(d->q_next_local) | at(d->q_next_target) | at(d->q_expected) | at(d->taus) | at(d->rewards) | at(d->dones) | at(d->out_grad_expected) | at(d->out_td_error)) & 3)
+        return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned float32 pointer (q_next_local, q_next_target, q_expected, taus, rewards, dones, out_grad_expected or out_td_error)");
+    if (d->action_type == SGW_PPO_ACT_I64 && (at(d->actions) & 7)) return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned int64 pointer (actions)");
+    if (at(d->valid) & (d->valid_type == SGW_POLICY_F64 ? 7 : 3)) return fail(SGW_EINVAL, "sgw_iqn_loss: valid is not aligned to its element type");
+    if ((at(d->out_terms) | at(d->out_next_actions) | at(d->out_row_terms) | at(d->workspace)) & 7)
+        return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned 8-byte pointer (out_terms, out_next_actions, out_row_terms or workspace)");
+    const int64_t widest = (int64_t)d->num_quantiles * std::max(d->num_actions, d->num_quantiles);
+    if (d->n > INT64_MAX / 8 / widest || d->n > INT64_MAX / 32)
+        return fail(SGW_EINVAL, "sgw_iqn_loss: n = %lld rows of %d x %d do not fit 64-bit offsets", (long long)d->n, d->num_quantiles, d->num_actions);
+    const unsigned blocks = (unsigned)iqn_loss_blocks(d->n, d->num_quantiles);
+    const int64_t need = (int64_t)blocks * (int64_t)sizeof(double);
+    if (need > 0 && (!d->workspace || d->workspace_bytes < need))
+        return fail(SGW_EINVAL, "sgw_iqn_loss: needs a workspace of %lld bytes (sgw_iqn_loss_workspace_bytes); got %lld", (long long)need, d->workspace ? (long long)d->workspace_bytes : 0ll);
+    if (d->n == 0) return SGW_OK;
+    IqnLossParams p{};
+    p.q_next_local = d->q_next_local; p.q_next_target = d->q_next_target; p.q_expected = d->q_expected; p.taus = d->taus;
+    p.actions = d->actions; p.rewards = d->rewards; p.dones = d->dones; p.valid = d->valid;
+    p.grad = d->out_grad_expected; p.next_actions = d->out_next_actions; p.row_terms = d->out_row_terms; p.td_error = d->out_td_error;
+    p.out_terms = d->out_terms; p.partials = static_cast<double*>(d->workspace);
+    p.n = d->n; p.tiles = iqn_loss_tiles(d->n, d->num_quantiles);
+    p.count = (double)(d->n * d->num_quantiles * d->num_quantiles);
+    p.inv = 1.0 / p.count;
+    p.discount = (float)d->discount;
+    p.N = d->num_quantiles; p.A = d->num_actions; p.atype = d->action_type; p.vtype = d->valid_type; p.nparts = (int32_t)blocks;
+    // 16 bytes per gradient store where a quad of actions lies inside one quantile's and every row starts on a 16-byte boundary
+    const bool vec = d->out_grad_expected && (d->num_actions & 3) == 0 && !(at(d->out_grad_expected) & 15);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_iqn_loss(p, vec, blocks, s);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(iqn_loss_merge_kernel, dim3(1), dim3(kBlock), 0, s, p);
     HIP_TRY(hipGetLastError());
     return SGW_OK;
 }

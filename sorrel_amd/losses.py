@@ -1,4 +1,6 @@
-"""PPO's clipped loss on the device (``sorrel/models/pytorch/ppo.py:259-285``: the body of ``PyTorchPPO.train_step``'s ``k_epochs`` loop
+"""The learners' loss heads on the device.
+
+PPO's clipped loss (``sorrel/models/pytorch/ppo.py:259-285``: the body of ``PyTorchPPO.train_step``'s ``k_epochs`` loop
 between the networks' outputs and ``optimizer.step``).
 
 ``ppo_loss_terms`` is one ``sgw_ppo_loss`` call (``sorrel_amd/csrc/ppo_loss.h``): it reads each row once and writes the loss terms and
@@ -9,7 +11,18 @@ the gradients of the mean loss at the actor's and the critic's outputs.  ``ppo_l
     optimizer.zero_grad(); loss.backward(); optimizer.step()
 
 ``_ppo_loss_torch`` is the reference's lines restated with torch ops: the path of CPU tensors, and what the kernel is compared with and
-timed against.  Device tensors always use the kernel.  The networks, the optimiser and the learner class stay the user's."""
+timed against.  Device tensors always use the kernel.  The networks, the optimiser and the learner class stay the user's.
+
+IQN's quantile Huber loss (``sorrel/models/pytorch/iqn.py:359-405``: the body of ``iRainbowModel.train_step`` between the three network
+outputs and ``loss.backward()``) has the same three forms -- ``iqn_loss_terms`` (one ``sgw_iqn_loss`` call, ``sorrel_amd/csrc/iqn_loss.h``),
+``iqn_loss`` and ``_iqn_loss_torch`` -- so a user's learner writes::
+
+    states, actions, rewards, next_states, dones, valid = buffer.sample(batch_size)
+    q_next_local, _ = local(next_states, n_quantiles); q_next_target, _ = target(next_states, n_quantiles)
+    q_expected, taus = local(states, n_quantiles)
+    loss = iqn_loss(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, GAMMA ** n_step)
+    optimizer.zero_grad(); loss.backward(); clip_grad_norm_(local.parameters(), 1); optimizer.step()
+"""
 from __future__ import annotations
 
 import ctypes as C
@@ -192,3 +205,169 @@ def ppo_loss(dist, values, actions, old_log_probs, returns, eps_clip, entropy_co
     if not torch.is_tensor(values):
         raise TypeError(f"values must be a tensor, not {type(values).__name__}")
     return _PPOLossFn.apply(t, values, logits, actions, old_log_probs, returns, eps_clip, entropy_coef, value_coef, out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- IQN's quantile Huber loss
+class IQNLoss:
+    """What ``iqn_loss_terms`` gives back: ``loss`` (0-d float64, a view of ``terms`` = ``[L]``), ``grad_expected`` (dL/d q_expected,
+    float32 ``[B, N, A]``, every element written), ``next_actions`` (int64 ``[B]``: the double-DQN choice ``a*``), and, if asked for,
+    ``row_terms`` (float64 ``[B]``: the rows' sums ``S_b``) and ``td_error`` (float32 ``[B, N, N]``: what a prioritised replay needs),
+    else None.  Passed back as ``out=`` its tensors are overwritten in place."""
+
+    __slots__ = ("terms", "loss", "grad_expected", "next_actions", "row_terms", "td_error", "_workspace")
+
+    def __init__(self, q_expected, row_terms=False, td_error=False):
+        dev = q_expected.device
+        B, N, _A = (int(s) for s in q_expected.shape)
+        self.terms = torch.empty((1,), dtype=torch.float64, device=dev)
+        self.loss = self.terms[0]
+        self.grad_expected = torch.empty(q_expected.shape, dtype=torch.float32, device=dev)
+        self.next_actions = torch.empty((B,), dtype=torch.int64, device=dev)
+        self.row_terms = torch.empty((B,), dtype=torch.float64, device=dev) if row_terms else None
+        self.td_error = torch.empty((B, N, N), dtype=torch.float32, device=dev) if td_error else None
+        self._workspace = None
+        if dev.type == "cuda":
+            from sorrel_amd import _native as N_
+
+            need = int(N_.load().sgw_iqn_loss_workspace_bytes(B, N))
+            self._workspace = torch.empty((max(need, 8) // 8,), dtype=torch.float64, device=dev)
+
+    def __repr__(self):
+        return f"IQNLoss(n={self.grad_expected.shape[0]}, num_quantiles={self.grad_expected.shape[1]}, num_actions={self.grad_expected.shape[2]})"
+
+
+def _check_iqn(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid):
+    for name, x in (("q_expected", q_expected), ("taus", taus), ("q_next_local", q_next_local), ("q_next_target", q_next_target),
+                    ("actions", actions), ("rewards", rewards), ("dones", dones), ("valid", valid)):
+        if not torch.is_tensor(x):
+            raise TypeError(f"{name} must be a tensor, not {type(x).__name__}")
+    if q_expected.dim() != 3:
+        raise ValueError(f"q_expected must be [B, N, A], not {tuple(q_expected.shape)}")
+    B, N, A = (int(s) for s in q_expected.shape)
+    if not 1 <= N <= 64:
+        raise ValueError(f"{N} quantiles: the loss takes 1..64")
+    if not 1 <= A <= 256:
+        raise ValueError(f"{A} actions: the loss takes 1..256")
+    f32 = (torch.float32,)
+    for name, x, dtypes, shapes in (
+            ("q_expected", q_expected, f32, ((B, N, A),)), ("q_next_local", q_next_local, f32, ((B, N, A),)),
+            ("q_next_target", q_next_target, f32, ((B, N, A),)), ("taus", taus, f32, ((B, N, 1), (B, N))),
+            ("actions", actions, (torch.int64, torch.uint8), ((B, 1), (B,))), ("rewards", rewards, f32, ((B, 1), (B,))),
+            ("dones", dones, f32, ((B, 1), (B,))), ("valid", valid, _FLOATS, ((B, 1), (B,)))):
+        if x.dtype not in dtypes:
+            raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, not {x.dtype}")
+        if tuple(x.shape) not in shapes:
+            raise ValueError(f"{name} has shape {tuple(x.shape)}; expected {' or '.join(str(list(s)) for s in shapes)}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if x.device != q_expected.device:
+            raise ValueError(f"{name} is on {x.device}, q_expected on {q_expected.device}")
+    return B, N, A
+
+
+def _check_iqn_out(out, q_expected, row_terms, td_error):
+    if not isinstance(out, IQNLoss):
+        raise TypeError("out= takes an earlier IQNLoss")
+    B, N, _A = (int(s) for s in q_expected.shape)
+    tensors = [out.terms, out.grad_expected, out.next_actions] + [x for x in (out.row_terms, out.td_error, out._workspace) if x is not None]
+    if (out.grad_expected.shape != q_expected.shape or any(x.device != q_expected.device for x in tensors)
+            or (row_terms and out.row_terms is None) or (td_error and out.td_error is None)
+            or (q_expected.device.type == "cuda" and out._workspace is None)):
+        raise ValueError("out= was made for other shapes or another device, or without the optional outputs asked for")
+    return out
+
+
+def _iqn_loss_torch(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount):
+    """The reference's lines (``iqn.py:359-402`` and ``calculate_huber_loss``) with torch ops: returns ``(loss, td_error, action_indx,
+    quantil_l)``, connected to ``q_expected`` for autograd.  ``discount`` is ``GAMMA ** n_step``."""
+    B, N, _A = q_expected.shape
+    actions, rewards, dones, valid = actions.reshape(B, 1).long(), rewards.reshape(B, 1), dones.reshape(B, 1), valid.reshape(B, 1)
+    taus = taus.reshape(B, N, 1)
+    action_indx = torch.argmax(q_next_local.detach().mean(dim=1), dim=1, keepdim=True)
+    Q_targets_next = q_next_target.detach().gather(2, action_indx.unsqueeze(-1).expand(B, N, 1)).transpose(1, 2)
+    Q_targets = rewards.unsqueeze(-1) + (discount * Q_targets_next * (1.0 - dones.unsqueeze(-1)))
+    Q_expected = q_expected.gather(2, actions.unsqueeze(-1).expand(B, N, 1))
+    td_error = Q_targets - Q_expected
+    huber_l = torch.where(td_error.abs() <= 1.0, 0.5 * td_error.pow(2), 1.0 * (td_error.abs() - 0.5 * 1.0))
+    huber_l = huber_l * valid.unsqueeze(-1)
+    quantil_l = abs(taus.detach() - (td_error.detach() < 0).float()) * huber_l / 1.0
+    return quantil_l.mean(), td_error, action_indx.reshape(B), quantil_l
+
+
+def _iqn_terms_by_torch(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount, res):
+    with torch.enable_grad():
+        leaf = q_expected.detach().requires_grad_(True)
+        L, td, a_star, ql = _iqn_loss_torch(leaf, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount)
+        (g,) = torch.autograd.grad(L, (leaf,))
+    res.terms.copy_(L.detach().double().reshape(1))
+    res.grad_expected.copy_(g)
+    res.next_actions.copy_(a_star)
+    if res.row_terms is not None:
+        res.row_terms.copy_(ql.detach().double().sum(dim=(1, 2)))
+    if res.td_error is not None:
+        res.td_error.copy_(td.detach())
+    return res
+
+
+def iqn_loss_terms(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount, *, out=None, row_terms=False,
+                   td_error=False):
+    """IQN's quantile Huber loss (kappa = 1) of a batch and its gradient at ``q_expected``: the three quantile tensors are contiguous
+    float32 ``[B, N, A]`` (the local net on the states, and the local and the target net on the next states), ``taus`` float32
+    ``[B, N, 1]`` or ``[B, N]`` (the taus of the ``q_expected`` call), ``actions`` (int64 / uint8), ``rewards``, ``dones`` (float32) and
+    ``valid`` (float32 / float64, any row weight) ``[B, 1]`` or ``[B]`` -- what ``Buffer.sample`` and ``TurnBuffer.sample`` hand over --
+    and ``discount`` is ``GAMMA ** n_step``.  Returns an ``IQNLoss``.  On a HIP device this is one ``sgw_iqn_loss`` call; with ``out=``
+    (an earlier result for the same shapes) it allocates nothing and does not synchronise, so it can be recorded into a graph.  A row
+    whose action is out of range gives NaN for its term, its gradient row and the loss."""
+    B, N, A = _check_iqn(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid)
+    discount = float(discount)
+    if discount != discount or discount in (float("inf"), float("-inf")):
+        raise ValueError(f"discount = {discount} must be finite")
+    res = IQNLoss(q_expected, row_terms, td_error) if out is None else _check_iqn_out(out, q_expected, row_terms, td_error)
+    if q_expected.device.type != "cuda":
+        return _iqn_terms_by_torch(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount, res)
+    if B == 0:
+        res.terms.fill_(float("nan"))                        # the mean of nothing, as torch's
+        return res
+    from sorrel_amd import _native as N_
+
+    d = N_.SgwIqnLossDesc()
+    d.q_next_local, d.q_next_target, d.q_expected, d.taus = q_next_local.data_ptr(), q_next_target.data_ptr(), q_expected.data_ptr(), taus.data_ptr()
+    d.actions, d.rewards, d.dones, d.valid = actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(), valid.data_ptr()
+    d.out_terms, d.out_grad_expected, d.out_next_actions = res.terms.data_ptr(), res.grad_expected.data_ptr(), res.next_actions.data_ptr()
+    if row_terms:
+        d.out_row_terms = res.row_terms.data_ptr()
+    if td_error:
+        d.out_td_error = res.td_error.data_ptr()
+    d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
+    d.n, d.num_quantiles, d.num_actions, d.discount = B, N, A, discount
+    d.action_type = N_.PPO_ACT_U8 if actions.dtype == torch.uint8 else N_.PPO_ACT_I64
+    d.valid_type = N_.POLICY_F64 if valid.dtype == torch.float64 else N_.POLICY_F32
+    with torch.cuda.device(q_expected.device):
+        N_.check(N_.load().sgw_iqn_loss(C.byref(d), C.c_void_p(torch.cuda.current_stream(q_expected.device).cuda_stream)))
+    return res
+
+
+class _IQNLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount, out):
+        res = iqn_loss_terms(q_expected.detach(), taus.detach(), q_next_local.detach(), q_next_target.detach(), actions, rewards, dones, valid,
+                             discount, out=out)
+        ctx.save_for_backward(res.grad_expected)
+        return res.loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        # one multiply: the incoming gradient is a device scalar (1 after loss.backward()) and is not read on the host
+        return (g * grad_out.to(g.dtype) if ctx.needs_input_grad[0] else None,) + (None,) * 9
+
+
+def iqn_loss(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount, *, out=None):
+    """``iqn_loss_terms`` as a differentiable scalar: the loss ``L`` (0-d float64), connected to ``q_expected`` only (nothing flows to
+    ``taus`` or to the next states' quantiles, as in the reference).  The forward launch has already written the gradient; ``backward``
+    multiplies it by the incoming gradient and hands it on.  ``out=``: an ``IQNLoss`` to reuse (it must not be overwritten before
+    ``backward`` ran)."""
+    for name, x in (("q_expected", q_expected), ("taus", taus), ("q_next_local", q_next_local), ("q_next_target", q_next_target)):
+        if not torch.is_tensor(x):
+            raise TypeError(f"{name} must be a tensor, not {type(x).__name__}")
+    return _IQNLossFn.apply(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, discount, out)
