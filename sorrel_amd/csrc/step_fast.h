@@ -4,8 +4,12 @@
 // ---------------------------------------------------------------- fast step kernel
 // Wave-per-env specialisation for worlds whose byte count is a multiple of 16 and
 // <= 4 KiB with at most one spawning type (all BASELINE configs up to 32x32x2):
-//   * the grid is loaded straight into registers (16 B per lane per unit) one env
-//     AHEAD of its use, so HBM latency hides under the previous env's work;
+//   * a wave takes ONE env and issues that env's grid loads first, straight into
+//     registers (16 B per lane per unit): their latency hides under the table set-up
+//     and under the other waves of the SIMD (there is no persistent loop, no prefetch);
+//   * what goes back is what the launch touched: the 16-byte units in which something
+//     spawned and each mover's old and new cell (whole-turn, sweep-only and act-only
+//     launches of plain compile-time shapes share that one write-back);
 //   * the Bernoulli half of the sweep runs on those registers (byte-parallel
 //     spawner match, one Philox block per dword); the rare "what spawns" draw is
 //     deferred to a short divergent loop that patches single bytes in LDS;
@@ -967,43 +971,40 @@ __device__ __forceinline__ void step_fast_body(const Params p, [[maybe_unused]] 
         if (tix + 1 < nturns) yx = moved ? npos : yx;   // the next turn starts where this one ended
         }   // turns
         if (dirty) {
-            if (!TAG && !RULES && !do_sweep && nturns == 1) {   // (a rollout's earlier turns moved other cells too)
-                // a policy-driven phase (no sweep, plain moves): only the movers' two cells changed -- write those bytes,
-                // not the whole grid (two movers touching one cell both write its FINAL content: no race)
+            // What a launch changed in a plain world's grid is known cell by cell: the cells in which something spawned (the spawn-kind patches of
+            // the sweep; `hits` has their units) and each mover's old and new cell (the agent loop's two bytes).  A whole turn of config 3 touches ~20 of
+            // the agents' layer's 1 024 bytes.  Every store below carries the FINAL content of the LDS copy, so a mover inside a hit unit, two movers on
+            // one cell or an agent stepping on what has just spawned write the same bytes twice: no race.
+            constexpr bool kTouched = kStatic && !RULES && !TAG && !MULTI;              // the write set above is complete: no tag, beam or earlier turn
+            const bool movers_only = !TAG && !RULES && !do_sweep && nturns == 1;        // a policy-driven phase (a rollout's earlier turns moved other cells too)
+            uint8_t* g = p.grid + env * p.env_stride;
+            if (!movers_only) {
+                uint4* dst = reinterpret_cast<uint4*>(g);
+#pragma unroll
+                for (int k = 0; k < NU; ++k) {
+                    // A full round of the register sweep (1 KiB at a multiple of 1 KiB inside the env) of a single-turn plain instance: a lane writes its
+                    // 16-byte unit only if something spawned in it -- a round without a hit issues no store at all (config 3: the Sand layer), the
+                    // movers' bytes follow below.  The same test serves the launch in which nobody acts (a policy-driven turn's first: the sweep alone
+                    // changed the grid; run-time shapes and dword-swept tail rounds stored their changed dwords as the sweep went).  Everything
+                    // else keeps the full store: dword-swept tail rounds and the ragged last round (its padding bytes were set above) of a whole
+                    // turn, Tag, layered rule sets, the turn loop (the hits are the last turn's only).
+                    const bool full_round = kTouched && k < kFullRounds && (k + 1) * 1024 <= TL * TH * TW;
+                    if (full_round || sweep_only) {
+                        if constexpr (kStatic)
+                            if (lane + 64 * k < nunits && hits[k]) dst[lane + 64 * k] = lg16[lane + 64 * k];
+                    } else if (lane + 64 * k < nunits) {
+                        dst[lane + 64 * k] = lg16[lane + 64 * k];
+                    }
+                }
+                if constexpr (RULES || !kStatic)
+                    if (!sweep_only)
+                        for (int i = 64 * NU + lane; i < nunits; i += 64) dst[i] = lg16[i];
+            }
+            if (kTouched || movers_only) {
                 if (mine && moved) {
-                    uint8_t* g = p.grid + env * p.env_stride;
                     g[oaddr_v] = lg[oaddr_v];
                     g[taddr_v] = lg[taddr_v];
                 }
-            } else if (sweep_only) {
-                // the sweep alone changed the grid (a policy-driven turn's first launch: nobody acts in it): write back only
-                // the 16-byte units in which something spawned -- ~4 of config 3's 128 units per env; the sweep-only launch
-                // is then a read of the grid plus a few scattered units instead of a read and a full write
-                // (run-time shapes: the dword sweep above stored its changed dwords as it went)
-                if constexpr (kStatic) {
-                    uint4* dst = reinterpret_cast<uint4*>(p.grid + env * p.env_stride);
-#pragma unroll
-                    for (int k = 0; k < NU; ++k)
-                        if (lane + 64 * k < nunits && hits[k]) dst[lane + 64 * k] = lg16[lane + 64 * k];
-                }
-            } else {
-                uint4* dst = reinterpret_cast<uint4*>(p.grid + env * p.env_stride);
-#pragma unroll
-                for (int k = 0; k < NU; ++k) {
-                    // A full round of the register sweep is 1 KiB at a multiple of 1 KiB inside the env (whole 128-byte lines where the env stride is a
-                    // multiple of 128, as for every map whose layers fill rounds): one in which nothing spawned and which holds no cell of the agents' layer still is what was loaded,
-                    // and stays where it is (config 3: the Sand layer, half of the grid bytes).  Single-turn launches only: the hits are the
-                    // last turn's.  A round with the ragged last unit is written (its padding bytes were set above).
-                    if constexpr (kStatic && !RULES && !TAG && !MULTI) {
-                        if (k < kFullRounds && (k + 1) * 1024 <= TL * TH * TW) {
-                            const bool agents_here = zoff < (k + 1) * 1024 && zoff + HW > k * 1024;
-                            if (!agents_here && __ballot(hits[k] != 0) == 0) continue;
-                        }
-                    }
-                    if (lane + 64 * k < nunits) dst[lane + 64 * k] = lg16[lane + 64 * k];
-                }
-                if constexpr (RULES || !kStatic)
-                    for (int i = 64 * NU + lane; i < nunits; i += 64) dst[i] = lg16[i];
             }
         }
         if (p.do_move) {
