@@ -29,8 +29,6 @@ constexpr int kIqnMaxQuantiles = 64;
 constexpr int kIqnMaxActions = 256;
 constexpr int kIqnNoAction = 0x7fffffff;      // the index of "no candidate yet": loses against every action
 
-typedef float iqn_f4 __attribute__((ext_vector_type(4)));
-
 struct IqnLossParams {
     const float* q_next_local;
     const float* q_next_target;
@@ -106,11 +104,11 @@ __global__ __launch_bounds__(kBlock) void iqn_loss_kernel(const IqnLossParams p)
         float rew = 0.0f, done = 0.0f, T = 0.0f, X = 0.0f, tau = 0.0f;
         double valid = 0.0;
         if (active) {
-            act = p.atype == SGW_PPO_ACT_U8 ? (int64_t)reinterpret_cast<const uint8_t*>(p.actions)[b] : reinterpret_cast<const int64_t*>(p.actions)[b];
+            act = load_action(p.actions, p.atype, b);
             bad = act < 0 || act >= A;
             rew = p.rewards[b];
             done = p.dones[b];
-            valid = p.vtype == SGW_POLICY_F64 ? reinterpret_cast<const double*>(p.valid)[b] : (double)reinterpret_cast<const float*>(p.valid)[b];
+            valid = load_float(p.valid, p.vtype, b);
             if (l < N) {
                 const float qt = p.q_next_target[base + (int64_t)l * A + besta];     // (besta is in [0, A): lane 0 always has a candidate)
                 const float dq = p.discount * qt;
@@ -165,12 +163,12 @@ __global__ __launch_bounds__(kBlock) void iqn_loss_kernel(const IqnLossParams p)
                     const float gv = __shfl(gval, i < N ? i : 0, G);
                     if (active && k < total) {
                         const int a0 = aq << 2;
-                        iqn_f4 o;
+                        cat_f4 o;
                         o.x = bad ? nan_f : ((int64_t)a0 == act ? gv : 0.0f);
                         o.y = bad ? nan_f : ((int64_t)(a0 + 1) == act ? gv : 0.0f);
                         o.z = bad ? nan_f : ((int64_t)(a0 + 2) == act ? gv : 0.0f);
                         o.w = bad ? nan_f : ((int64_t)(a0 + 3) == act ? gv : 0.0f);
-                        __builtin_nontemporal_store(o, reinterpret_cast<iqn_f4*>(p.grad + base) + k);
+                        __builtin_nontemporal_store(o, reinterpret_cast<cat_f4*>(p.grad + base) + k);
                     }
                     k += G; i += di; aq += da;
                     if (aq >= Aq) { aq -= Aq; ++i; }
@@ -189,29 +187,19 @@ __global__ __launch_bounds__(kBlock) void iqn_loss_kernel(const IqnLossParams p)
         }
     }
     // the workgroup's sum: a pairwise tree whose order depends on nothing but the thread index
-    __shared__ double red[kBlock];
-    red[tid] = sum;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) p.partials[blockIdx.x] = red[0];
+    __shared__ double red[1][kBlock];
+    const double sums[1] = {sum};
+    block_tree<1>(sums, red, TreeSum{});
+    if (tid == 0) p.partials[blockIdx.x] = red[0][0];
 }
 
 // second launch, one workgroup: thread i adds partials i, i + 256, ... in that order, the same tree merges the threads, thread 0 writes L
 __global__ __launch_bounds__(kBlock) void iqn_loss_merge_kernel(const IqnLossParams p) {
-    __shared__ double red[kBlock];
-    const int tid = threadIdx.x;
-    double a = 0.0;
-    for (int i = tid; i < p.nparts; i += kBlock) a += p.partials[i];
-    red[tid] = a;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) p.out_terms[0] = red[0] / p.count;
+    __shared__ double red[1][kBlock];
+    double sums[1];
+    partials_sum<1>(p.partials, p.nparts, sums);
+    block_tree<1>(sums, red, TreeSum{});
+    if (threadIdx.x == 0) p.out_terms[0] = red[0][0] / p.count;
 }
 
 // host side

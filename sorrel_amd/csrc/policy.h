@@ -31,18 +31,6 @@ struct PolicyParams {
     uint32_t seed_lo, seed_hi, first_env, epoch, turn;
 };
 
-__device__ __forceinline__ double policy_clamped_log(const double q) {
-    // torch's probs_to_logits: log(clamp(q, eps, 1 - eps)) with eps = 2^-52 (a NaN passes through both comparisons)
-    constexpr double lo = 0x1p-52, hi = 1.0 - 0x1p-52;
-    return log(q < lo ? lo : (q > hi ? hi : q));
-}
-
-template <bool F64>
-__device__ __forceinline__ double policy_elem(const void* base, const int64_t at) {
-    if constexpr (F64) return reinterpret_cast<const double*>(base)[at];
-    else return (double)reinterpret_cast<const float*>(base)[at];
-}
-
 // NA: 4 / 8 / 16 = the register-resident buckets (nact <= NA), 0 = the generic loop (nact <= 256).  VEC: 16-byte loads.
 template <int NA, bool F64, bool VEC>
 __global__ __launch_bounds__(kBlock) void policy_sample_kernel(const PolicyParams p) {
@@ -81,40 +69,9 @@ __global__ __launch_bounds__(kBlock) void policy_sample_kernel(const PolicyParam
         if constexpr (NA > 0) {
             double x[NA];
             const double pad = logits ? -inf : 0.0;   // a weight of exactly 0: never chosen, adds nothing to any sum
-            if constexpr (VEC) {
-                constexpr int PER = F64 ? 2 : 4;
-#pragma unroll
-                for (int c = 0; c < NA / PER; ++c) {
-                    if (c * PER < nact) {             // (nact is a multiple of PER on this path)
-                        if constexpr (F64) {
-                            const double2 v = reinterpret_cast<const double2*>(reinterpret_cast<const double*>(p.dist) + at0)[c];
-                            x[2 * c] = v.x; x[2 * c + 1] = v.y;
-                        } else {
-                            const float4 v = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.dist) + at0)[c];
-                            x[4 * c] = (double)v.x; x[4 * c + 1] = (double)v.y; x[4 * c + 2] = (double)v.z; x[4 * c + 3] = (double)v.w;
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < PER; ++j) x[PER * c + j] = pad;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NA; ++i) x[i] = i < nact ? policy_elem<F64>(p.dist, at0 + i) : pad;
-            }
-            if (logits) {
-                double m = x[0];
-#pragma unroll
-                for (int i = 1; i < NA; ++i) m = x[i] > m || m != m ? x[i] : m;      // (a NaN is replaced; a NaN entry gives a NaN weight below)
-                bad |= !(m < inf);
-#pragma unroll
-                for (int i = 0; i < NA; ++i) x[i] = exp(x[i] - m);
-            }
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                bad |= !(x[i] >= 0.0);
-                S += x[i];
-            }
+            cat_load_row<NA, F64, VEC>(p.dist, at0, nact, pad, x);
+            if (logits) bad |= cat_weights<NA>(x);
+            S = cat_sum<NA>(x, bad);
             const double t = uh * S;
             double c = 0.0;
             bool found = false;
@@ -136,16 +93,11 @@ __global__ __launch_bounds__(kBlock) void policy_sample_kernel(const PolicyParam
         } else {
             double m = 0.0;
             if (logits) {
-                m = policy_elem<F64>(p.dist, at0);
-                for (int i = 1; i < nact; ++i) {
-                    const double v = policy_elem<F64>(p.dist, at0 + i);
-                    m = v > m || m != m ? v : m;
-                }
+                m = cat_row_max<F64>(p.dist, at0, nact);
                 bad |= !(m < inf);
             }
             for (int i = 0; i < nact; ++i) {
-                const double v = policy_elem<F64>(p.dist, at0 + i);
-                const double w = logits ? exp(v - m) : v;
+                const double w = cat_weight<F64>(p.dist, at0 + i, logits, m);
                 bad |= !(w >= 0.0);
                 S += w;
             }
@@ -154,8 +106,7 @@ __global__ __launch_bounds__(kBlock) void policy_sample_kernel(const PolicyParam
             bool found = false;
             const bool ent = p.out_entropy != nullptr;
             for (int i = 0; i < nact; ++i) {
-                const double v = policy_elem<F64>(p.dist, at0 + i);
-                const double w = logits ? exp(v - m) : v;
+                const double w = cat_weight<F64>(p.dist, at0 + i, logits, m);
                 c += w;
                 if (!found && c > t) { found = true; action = i; wa = w; }
                 if (ent) {
@@ -179,17 +130,5 @@ __global__ __launch_bounds__(kBlock) void policy_sample_kernel(const PolicyParam
 // host side
 template <bool F64>
 void launch_policy(const PolicyParams& p, const bool vec, const unsigned blocks, hipStream_t s) {
-    const int n = p.nact;
-    if (n <= 4) {
-        if (vec) hipLaunchKernelGGL((policy_sample_kernel<4, F64, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((policy_sample_kernel<4, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else if (n <= 8) {
-        if (vec) hipLaunchKernelGGL((policy_sample_kernel<8, F64, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((policy_sample_kernel<8, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else if (n <= 16) {
-        if (vec) hipLaunchKernelGGL((policy_sample_kernel<16, F64, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((policy_sample_kernel<16, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else {
-        hipLaunchKernelGGL((policy_sample_kernel<0, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    }
+    dispatch_actions(p.nact, vec, [&](auto na, auto v) { hipLaunchKernelGGL((policy_sample_kernel<na(), F64, v()>), dim3(blocks), dim3(kBlock), 0, s, p); });
 }

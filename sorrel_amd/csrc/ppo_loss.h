@@ -19,9 +19,6 @@
 constexpr int kPpoMaxBlocks = 2048;           // grid cap: 8 workgroups per CU on 256 CUs; more row tiles than that and the workgroups stride
 constexpr int kPpoMaxActions = 256;
 
-typedef float ppo_f4 __attribute__((ext_vector_type(4)));
-typedef double ppo_d2 __attribute__((ext_vector_type(2)));
-
 struct PpoLossParams {
     const void* dist;
     const void* values;
@@ -37,10 +34,6 @@ struct PpoLossParams {
     double lo, hi, c, vc;
     int32_t nact, mode, vtype, atype, rtype, nparts;
 };
-
-__device__ __forceinline__ double ppo_scalar(const void* base, const int type, const int64_t k) {
-    return type == SGW_POLICY_F64 ? reinterpret_cast<const double*>(base)[k] : (double)reinterpret_cast<const float*>(base)[k];
-}
 
 // gq_i of include/sgw.h for one weight: q = w / S, l = the clamped log; at the action taken (`taken`) gr r is subtracted from c q
 // (a subtraction IS the addition of the negation, and no unary minus is left for the optimiser to fold into the product gr r)
@@ -99,50 +92,20 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
         const int64_t k = tile * kBlock + threadIdx.x;
         if (k >= p.n) continue;                   // (the barrier sits behind the loop: a lane past the last row simply adds nothing)
         const int64_t at0 = k * p.stride;
-        const int64_t act = p.atype == SGW_PPO_ACT_U8 ? (int64_t)reinterpret_cast<const uint8_t*>(p.actions)[k] : reinterpret_cast<const int64_t*>(p.actions)[k];
-        const double v = ppo_scalar(p.values, p.vtype, k), R = ppo_scalar(p.returns, p.rtype, k), old = (double)p.old_lp[k];
+        const int64_t act = load_action(p.actions, p.atype, k);
+        const double v = load_float(p.values, p.vtype, k), R = load_float(p.returns, p.rtype, k), old = (double)p.old_lp[k];
         bool bad = act < 0 || act >= nact;
         double S = 0.0, acc = 0.0;
         PpoRow row;
         if constexpr (NA > 0) {
             double x[NA], g[NA];
             const double pad = logits ? -inf : 0.0;   // a weight of exactly 0: adds nothing to any sum
-            if constexpr (VEC) {
-                constexpr int PER = F64 ? 2 : 4;
-#pragma unroll
-                for (int cc = 0; cc < NA / PER; ++cc) {
-                    if (cc * PER < nact) {            // (nact is a multiple of PER on this path)
-                        if constexpr (F64) {
-                            const ppo_d2 q2 = reinterpret_cast<const ppo_d2*>(reinterpret_cast<const double*>(p.dist) + at0)[cc];
-                            x[2 * cc] = q2.x; x[2 * cc + 1] = q2.y;
-                        } else {
-                            const ppo_f4 q4 = reinterpret_cast<const ppo_f4*>(reinterpret_cast<const float*>(p.dist) + at0)[cc];
-                            x[4 * cc] = (double)q4.x; x[4 * cc + 1] = (double)q4.y; x[4 * cc + 2] = (double)q4.z; x[4 * cc + 3] = (double)q4.w;
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < PER; ++j) x[PER * cc + j] = pad;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NA; ++i) x[i] = i < nact ? policy_elem<F64>(p.dist, at0 + i) : pad;
-            }
-            if (logits) {
-                double m = x[0];
-#pragma unroll
-                for (int i = 1; i < NA; ++i) m = x[i] > m || m != m ? x[i] : m;      // (a NaN is replaced; a NaN entry gives a NaN weight below)
-                bad |= !(m < inf);
-#pragma unroll
-                for (int i = 0; i < NA; ++i) x[i] = exp(x[i] - m);
-            }
+            cat_load_row<NA, F64, VEC>(p.dist, at0, nact, pad, x);
+            if (logits) bad |= cat_weights<NA>(x);
+            S = cat_sum<NA>(x, bad);
             double wa = 0.0;
 #pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                bad |= !(x[i] >= 0.0);
-                S += x[i];
-                wa = (int64_t)i == act ? x[i] : wa;  // (a select per element: no register array is indexed by a lane's value)
-            }
+            for (int i = 0; i < NA; ++i) wa = (int64_t)i == act ? x[i] : wa;      // (a select per element: no register array is indexed by a lane's value)
             bad |= !(S > 0.0 && S < inf);
             row = ppo_row_scalars(p, policy_clamped_log(wa / S), old, v, R, dn);
             double t = 0.0;
@@ -173,56 +136,25 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
                     }
                     g[i] = bad ? nan_ : o;
                 }
-                if constexpr (VEC) {
-                    constexpr int PER = F64 ? 2 : 4;
-#pragma unroll
-                    for (int cc = 0; cc < NA / PER; ++cc) {
-                        if (cc * PER < nact) {
-                            if constexpr (F64) {
-                                ppo_d2 o2;
-                                o2.x = g[2 * cc]; o2.y = g[2 * cc + 1];
-                                __builtin_nontemporal_store(o2, reinterpret_cast<ppo_d2*>(reinterpret_cast<double*>(p.g_dist) + at0) + cc);
-                            } else {
-                                ppo_f4 o4;
-                                o4.x = (float)g[4 * cc]; o4.y = (float)g[4 * cc + 1]; o4.z = (float)g[4 * cc + 2]; o4.w = (float)g[4 * cc + 3];
-                                __builtin_nontemporal_store(o4, reinterpret_cast<ppo_f4*>(reinterpret_cast<float*>(p.g_dist) + at0) + cc);
-                            }
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < NA; ++i) {
-                        if (i < nact) {
-                            if constexpr (F64) __builtin_nontemporal_store(g[i], reinterpret_cast<double*>(p.g_dist) + at0 + i);
-                            else __builtin_nontemporal_store((float)g[i], reinterpret_cast<float*>(p.g_dist) + at0 + i);
-                        }
-                    }
-                }
+                cat_store_row<NA, F64, VEC>(p.g_dist, at0, nact, g);
             }
         } else {
             double m = 0.0;
             if (logits) {
-                m = policy_elem<F64>(p.dist, at0);
-                for (int i = 1; i < nact; ++i) {
-                    const double e = policy_elem<F64>(p.dist, at0 + i);
-                    m = e > m || m != m ? e : m;
-                }
+                m = cat_row_max<F64>(p.dist, at0, nact);
                 bad |= !(m < inf);
             }
             for (int i = 0; i < nact; ++i) {
-                const double e = policy_elem<F64>(p.dist, at0 + i);
-                const double w = logits ? exp(e - m) : e;
+                const double w = cat_weight<F64>(p.dist, at0 + i, logits, m);
                 bad |= !(w >= 0.0);
                 S += w;
             }
             bad |= !(S > 0.0 && S < inf);
-            const double ea = policy_elem<F64>(p.dist, at0 + (act < 0 || act >= nact ? 0 : act));    // (an action out of range reads element 0; the row is NaN)
-            const double wa = logits ? exp(ea - m) : ea;
+            const double wa = cat_weight<F64>(p.dist, at0 + (act < 0 || act >= nact ? 0 : act), logits, m);    // (an action out of range reads element 0; the row is NaN)
             row = ppo_row_scalars(p, policy_clamped_log(wa / S), old, v, R, dn);
             double t = 0.0;
             for (int i = 0; i < nact; ++i) {
-                const double e = policy_elem<F64>(p.dist, at0 + i);
-                const double w = logits ? exp(e - m) : e;
+                const double w = cat_weight<F64>(p.dist, at0 + i, logits, m);
                 double q, l;
                 const double gq = ppo_gq(w, S, c, row.grr, (int64_t)i == act, q, l);
                 const double ql = q * l;
@@ -232,8 +164,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
             }
             if (p.g_dist) {
                 for (int i = 0; i < nact; ++i) {
-                    const double e = policy_elem<F64>(p.dist, at0 + i);
-                    const double w = logits ? exp(e - m) : e;
+                    const double w = cat_weight<F64>(p.dist, at0 + i, logits, m);
                     double q, l;
                     const double diff = ppo_gq(w, S, c, row.grr, (int64_t)i == act, q, l) - t;
                     double o;
@@ -244,9 +175,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
                         const double per = diff / S;
                         o = per / dn;
                     }
-                    o = bad ? nan_ : o;
-                    if constexpr (F64) __builtin_nontemporal_store(o, reinterpret_cast<double*>(p.g_dist) + at0 + i);
-                    else __builtin_nontemporal_store((float)o, reinterpret_cast<float*>(p.g_dist) + at0 + i);
+                    policy_store_elem<F64>(p.g_dist, at0 + i, bad ? nan_ : o);
                 }
             }
         }
@@ -255,10 +184,7 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
         sumP += P;
         sumD += d2;
         sumH += H;
-        if (p.g_values) {
-            if (p.vtype == SGW_POLICY_F64) __builtin_nontemporal_store(gv, reinterpret_cast<double*>(p.g_values) + k);
-            else __builtin_nontemporal_store((float)gv, reinterpret_cast<float*>(p.g_values) + k);
-        }
+        if (p.g_values) store_float(p.g_values, p.vtype, k, gv);
         if (p.row_terms) {
             __builtin_nontemporal_store(P, p.row_terms + 3 * k);
             __builtin_nontemporal_store(d2, p.row_terms + 3 * k + 1);
@@ -267,20 +193,9 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
     }
     // the workgroup's sums: a pairwise tree whose order depends on nothing but the thread index
     __shared__ double red[3][kBlock];
-    const int tid = threadIdx.x;
-    red[0][tid] = sumP;
-    red[1][tid] = sumD;
-    red[2][tid] = sumH;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-            red[2][tid] += red[2][tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
+    const double sums[3] = {sumP, sumD, sumH};
+    block_tree<3>(sums, red, TreeSum{});
+    if (threadIdx.x == 0) {
         p.partials[3 * blockIdx.x] = red[0][0];
         p.partials[3 * blockIdx.x + 1] = red[1][0];
         p.partials[3 * blockIdx.x + 2] = red[2][0];
@@ -292,26 +207,10 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(const PpoLossParams p)
 __global__ __launch_bounds__(kBlock) void ppo_loss_merge_kernel(const PpoLossParams p) {
 #pragma clang fp contract(off)
     __shared__ double red[3][kBlock];
-    const int tid = threadIdx.x;
-    double a = 0.0, b = 0.0, h = 0.0;
-    for (int i = tid; i < p.nparts; i += kBlock) {
-        a += p.partials[3 * i];
-        b += p.partials[3 * i + 1];
-        h += p.partials[3 * i + 2];
-    }
-    red[0][tid] = a;
-    red[1][tid] = b;
-    red[2][tid] = h;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-            red[2][tid] += red[2][tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
+    double sums[3];
+    partials_sum<3>(p.partials, p.nparts, sums);
+    block_tree<3>(sums, red, TreeSum{});
+    if (threadIdx.x == 0) {
         const double dn = (double)p.n;
         const double Pm = red[0][0] / dn, M = red[1][0] / dn, Hm = red[2][0] / dn;
         const double vm = p.vc * M;
@@ -329,17 +228,5 @@ inline int64_t ppo_loss_blocks(const int64_t n) { return std::min<int64_t>((n + 
 
 template <bool F64>
 void launch_ppo_loss(const PpoLossParams& p, const bool vec, const unsigned blocks, hipStream_t s) {
-    const int n = p.nact;
-    if (n <= 4) {
-        if (vec) hipLaunchKernelGGL((ppo_loss_kernel<4, F64, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((ppo_loss_kernel<4, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else if (n <= 8) {
-        if (vec) hipLaunchKernelGGL((ppo_loss_kernel<8, F64, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((ppo_loss_kernel<8, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else if (n <= 16) {
-        if (vec) hipLaunchKernelGGL((ppo_loss_kernel<16, F64, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((ppo_loss_kernel<16, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else {
-        hipLaunchKernelGGL((ppo_loss_kernel<0, F64, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    }
+    dispatch_actions(p.nact, vec, [&](auto na, auto v) { hipLaunchKernelGGL((ppo_loss_kernel<na(), F64, v()>), dim3(blocks), dim3(kBlock), 0, s, p); });
 }

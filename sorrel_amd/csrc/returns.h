@@ -58,21 +58,15 @@ __device__ __forceinline__ Moments moments_merge(const Moments a, const Moments 
 }
 
 // the workgroup's moments, merged pairwise in an order that depends on nothing but the thread index; every thread gets the result
+// (block_reduce.h's tree with moments_merge as its operation; like moments_push and moments_merge, WITHOUT fp contract off)
 __device__ __forceinline__ Moments moments_block_merge(const Moments m, double (*red)[kBlock]) {
-    const int tid = threadIdx.x;
-    red[0][tid] = m.n;
-    red[1][tid] = m.mean;
-    red[2][tid] = m.m2;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            const Moments r = moments_merge(Moments{red[0][tid], red[1][tid], red[2][tid]}, Moments{red[0][tid + s], red[1][tid + s], red[2][tid + s]});
-            red[0][tid] = r.n;
-            red[1][tid] = r.mean;
-            red[2][tid] = r.m2;
-        }
-        __syncthreads();
-    }
+    const double v[3] = {m.n, m.mean, m.m2};
+    block_tree<3>(v, red, [](double (&a)[3], const double (&b)[3]) {
+        const Moments r = moments_merge(Moments{a[0], a[1], a[2]}, Moments{b[0], b[1], b[2]});
+        a[0] = r.n;
+        a[1] = r.mean;
+        a[2] = r.m2;
+    });
     return Moments{red[0][0], red[1][0], red[2][0]};
 }
 

@@ -54,6 +54,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -66,11 +67,13 @@ namespace {
 #include "step_fast.h"
 #include "step_big.h"
 #include "phase.h"
+#include "block_reduce.h"
 #include "small_kernels.h"
 #include "resolve.h"
 #include "render.h"
 #include "sample.h"
 #include "returns.h"
+#include "categorical.h"
 #include "policy.h"
 #include "ppo_loss.h"
 #include "iqn_loss.h"
@@ -94,6 +97,25 @@ int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) return fail(SGW_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss) ask of their arguments
+inline uintptr_t at(const void* q) { return reinterpret_cast<uintptr_t>(q); }
+// is any of these pointers off the alignment `mask` + 1?  (NULL, an optional argument or one of another type, is aligned to everything)
+inline bool misaligned(const uintptr_t mask, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= at(q);
+    return (bits & mask) != 0;
+}
+inline bool is_float_type(const int32_t t) { return t == SGW_POLICY_F32 || t == SGW_POLICY_F64; }
+inline uintptr_t float_mask(const int32_t t) { return t == SGW_POLICY_F64 ? 7 : 3; }
+// SGW_OK, or the refusal of a workspace that is missing or smaller than `need` bytes (`when`: the case that needs one, if not every call does)
+int workspace_short(const char* who, const void* ptr, const int64_t have, const int64_t need, const char* when = "") {
+    if (need <= 0 || (ptr && have >= need)) return SGW_OK;
+    return fail(SGW_EINVAL, "%s:%s needs a workspace of %lld bytes (%s_workspace_bytes); got %lld", who, when, (long long)need, who, ptr ? (long long)have : 0ll);
+}
+
+// one launch of kBlock-thread workgroups and the check behind it (a failure reads "hipGetLastError(): ...", as it always has)
+#define LAUNCH_TRY(kernel, blocks, s, p) do { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, p); HIP_TRY(hipGetLastError()); } while (0)
 
 constexpr int kEventPool = 4096;
 
@@ -1264,11 +1286,10 @@ int sgw_sample(const sgw_sample_desc* d, void* stream) {
     if (!d->starts != !d->envs) return fail(SGW_EINVAL, "sgw_sample: starts and envs are both given or both NULL");
     if (d->src_type != SGW_SAMPLE_F32 && d->src_type != SGW_SAMPLE_U8) return fail(SGW_EINVAL, "sgw_sample: unknown src_type %d", d->src_type);
     if (d->act_type != SGW_SAMPLE_ACT_I64 && d->act_type != SGW_SAMPLE_ACT_U8) return fail(SGW_EINVAL, "sgw_sample: unknown act_type %d", d->act_type);
-    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
     const bool u8 = d->src_type == SGW_SAMPLE_U8;
-    if (((u8 ? 0 : at(d->states)) | at(d->rewards) | at(d->dones) | at(d->out_states) | at(d->out_next_states) | at(d->out_rewards) | at(d->out_dones) | at(d->out_valid)) & 3)
+    if (misaligned(3, {u8 ? nullptr : d->states, d->rewards, d->dones, d->out_states, d->out_next_states, d->out_rewards, d->out_dones, d->out_valid}))
         return fail(SGW_EINVAL, "sgw_sample: misaligned float32 pointer");
-    if (((d->act_type == SGW_SAMPLE_ACT_I64 ? at(d->actions) : 0) | at(d->starts) | at(d->envs) | at(d->draw_count) | at(d->out_actions) | at(d->out_index)) & 7)
+    if (misaligned(7, {d->act_type == SGW_SAMPLE_ACT_I64 ? d->actions : nullptr, d->starts, d->envs, d->draw_count, d->out_actions, d->out_index}))
         return fail(SGW_EINVAL, "sgw_sample: misaligned int64 pointer");
     if (d->n > INT64_MAX / ((int64_t)d->n_frames + 1) / d->row_elems) return fail(SGW_EINVAL, "sgw_sample: n = %lld: the batch does not fit 64-bit offsets", (long long)d->n);
     if (d->n == 0) return SGW_OK;
@@ -1294,14 +1315,10 @@ int sgw_sample(const sgw_sample_desc* d, void* stream) {
     p.step_k = waves / (d->n_frames + 1);
     p.step_j = (int32_t)(waves % (d->n_frames + 1));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vec4) {
-        if (u8) hipLaunchKernelGGL((sample_rows_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((sample_rows_kernel<4, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    } else {
-        if (u8) hipLaunchKernelGGL((sample_rows_kernel<1, true>), dim3(blocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((sample_rows_kernel<1, false>), dim3(blocks), dim3(kBlock), 0, s, p);
-    }
-    HIP_TRY(hipGetLastError());
+    if (vec4 && u8) LAUNCH_TRY((sample_rows_kernel<4, true>), blocks, s, p);
+    else if (vec4) LAUNCH_TRY((sample_rows_kernel<4, false>), blocks, s, p);
+    else if (u8) LAUNCH_TRY((sample_rows_kernel<1, true>), blocks, s, p);
+    else LAUNCH_TRY((sample_rows_kernel<1, false>), blocks, s, p);
     if (!d->starts && d->draw_count) {
         hipLaunchKernelGGL(sample_count_kernel, dim3(1), dim3(64), 0, s, d->draw_count);
         HIP_TRY(hipGetLastError());
@@ -1330,18 +1347,14 @@ int sgw_returns(const sgw_returns_desc* d, void* stream) {
     if (d->first < 0 || d->first >= d->capacity) return fail(SGW_EINVAL, "sgw_returns: first = %lld outside [0, capacity = %lld)", (long long)d->first, (long long)d->capacity);
     if (d->cols < 1 || d->cols >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_returns: cols = %lld outside [1, 2^31)", (long long)d->cols);
     if (d->turn_stride < 1 || d->col_stride < 1) return fail(SGW_EINVAL, "sgw_returns: turn_stride = %lld, col_stride = %lld: strides must be at least 1", (long long)d->turn_stride, (long long)d->col_stride);
-    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-    if ((at(d->rewards) | at(d->dones) | at(d->out_returns) | (out32 ? at(d->out_normalized) : 0)) & 3) return fail(SGW_EINVAL, "sgw_returns: misaligned float32 pointer");
-    if (((out32 ? 0 : at(d->out_normalized)) | at(d->out_stats) | at(d->workspace)) & 7) return fail(SGW_EINVAL, "sgw_returns: misaligned float64 pointer");
+    if (misaligned(3, {d->rewards, d->dones, d->out_returns, out32 ? d->out_normalized : nullptr})) return fail(SGW_EINVAL, "sgw_returns: misaligned float32 pointer");
+    if (misaligned(7, {out32 ? nullptr : d->out_normalized, d->out_stats, d->workspace})) return fail(SGW_EINVAL, "sgw_returns: misaligned float64 pointer");
     // the largest element offset read, capacity * turn_stride + cols * col_stride, and the largest byte offset written, 8 * count * cols
     if (d->capacity > INT64_MAX / 2 / d->turn_stride || d->cols > INT64_MAX / 2 / d->col_stride || d->count > INT64_MAX / 16 / d->cols)
         return fail(SGW_EINVAL, "sgw_returns: capacity = %lld, cols = %lld with strides %lld / %lld do not fit 64-bit offsets", (long long)d->capacity, (long long)d->cols, (long long)d->turn_stride, (long long)d->col_stride);
     const unsigned blocks = (unsigned)returns_blocks(d->cols);
-    if (d->normalize == SGW_RETURNS_NORM_ALL) {
-        const int64_t need = (int64_t)blocks * 3 * (int64_t)sizeof(double);
-        if (!d->workspace || d->workspace_bytes < need)
-            return fail(SGW_EINVAL, "sgw_returns: SGW_RETURNS_NORM_ALL needs a workspace of %lld bytes (sgw_returns_workspace_bytes); got %lld", (long long)need, d->workspace ? (long long)d->workspace_bytes : 0ll);
-    }
+    if (d->normalize == SGW_RETURNS_NORM_ALL)
+        if (int rc = workspace_short("sgw_returns", d->workspace, d->workspace_bytes, (int64_t)blocks * 3 * (int64_t)sizeof(double), " SGW_RETURNS_NORM_ALL")) return rc;
     if (d->count == 0) return SGW_OK;
     ReturnsParams p{};
     p.rewards = d->rewards; p.dones = d->dones; p.out_returns = d->out_returns; p.out_norm = d->out_normalized; p.out_stats = d->out_stats;
@@ -1357,9 +1370,8 @@ int sgw_returns(const sgw_returns_desc* d, void* stream) {
     HIP_TRY(hipGetLastError());
     if (d->normalize == SGW_RETURNS_NORM_ALL) {
         const unsigned nblocks = (unsigned)std::min<int64_t>(ceil_div(d->count * d->cols, kBlock * 4), kReturnsMaxBlocks);
-        if (out32) hipLaunchKernelGGL((returns_normalize_all_kernel<true>), dim3(nblocks), dim3(kBlock), 0, s, p);
-        else hipLaunchKernelGGL((returns_normalize_all_kernel<false>), dim3(nblocks), dim3(kBlock), 0, s, p);
-        HIP_TRY(hipGetLastError());
+        if (out32) LAUNCH_TRY(returns_normalize_all_kernel<true>, nblocks, s, p);
+        else LAUNCH_TRY(returns_normalize_all_kernel<false>, nblocks, s, p);
     }
     return SGW_OK;
 }
@@ -1371,7 +1383,7 @@ static int policy_launch(const sgw_policy_desc* d, const TurnState* ts, const ch
     if (d->num_actions < 1 || d->num_actions > kPolicyMaxActions) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, d->num_actions, kPolicyMaxActions);
     if (d->num_envs < 1) return fail(SGW_EINVAL, "%s: num_envs = %lld", who, (long long)d->num_envs);
     if (d->row_stride < d->num_actions) return fail(SGW_EINVAL, "%s: row_stride = %lld is smaller than num_actions = %d", who, (long long)d->row_stride, d->num_actions);
-    if (d->dist_type != SGW_POLICY_F32 && d->dist_type != SGW_POLICY_F64) return fail(SGW_EINVAL, "%s: unknown dist_type %d", who, d->dist_type);
+    if (!is_float_type(d->dist_type)) return fail(SGW_EINVAL, "%s: unknown dist_type %d", who, d->dist_type);
     if (d->mode != SGW_POLICY_PROBS && d->mode != SGW_POLICY_LOGITS) return fail(SGW_EINVAL, "%s: unknown mode %d", who, d->mode);
     if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
     if (d->epoch >= (1u << 28)) return fail(SGW_EINVAL, "%s: epoch must be < 2^28", who);
@@ -1380,12 +1392,11 @@ static int policy_launch(const sgw_policy_desc* d, const TurnState* ts, const ch
         if (d->agent0 < 0 || last >= SGW_MAX_AGENTS)
             return fail(SGW_EINVAL, "%s: rows are keyed by agents %d .. %lld, outside [0, %d)", who, d->agent0, (long long)last, SGW_MAX_AGENTS);
     }
-    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
     const bool f64 = d->dist_type == SGW_POLICY_F64;
     const int64_t esz = f64 ? 8 : 4;
-    if (at(d->dist) & (uintptr_t)(esz - 1)) return fail(SGW_EINVAL, "%s: dist is not aligned to its element type", who);
-    if ((at(d->out_log_probs) | at(d->out_entropy)) & 3) return fail(SGW_EINVAL, "%s: misaligned float32 pointer", who);
-    if ((at(d->out_actions) | at(d->idx)) & 7) return fail(SGW_EINVAL, "%s: misaligned int64 pointer", who);
+    if (misaligned(float_mask(d->dist_type), {d->dist})) return fail(SGW_EINVAL, "%s: dist is not aligned to its element type", who);
+    if (misaligned(3, {d->out_log_probs, d->out_entropy})) return fail(SGW_EINVAL, "%s: misaligned float32 pointer", who);
+    if (misaligned(7, {d->out_actions, d->idx})) return fail(SGW_EINVAL, "%s: misaligned int64 pointer", who);
     if (d->n > INT64_MAX / 8 / d->row_stride) return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->row_stride);
     if (d->n == 0) return SGW_OK;
     PolicyParams p{};
@@ -1438,27 +1449,22 @@ int sgw_ppo_loss(const sgw_ppo_loss_desc* d, void* stream) {
     if (d->n < 0) return fail(SGW_EINVAL, "sgw_ppo_loss: n = %lld", (long long)d->n);
     if (d->num_actions < 1 || d->num_actions > kPpoMaxActions) return fail(SGW_EINVAL, "sgw_ppo_loss: num_actions = %d outside [1, %d]", d->num_actions, kPpoMaxActions);
     if (d->row_stride < d->num_actions) return fail(SGW_EINVAL, "sgw_ppo_loss: row_stride = %lld is smaller than num_actions = %d", (long long)d->row_stride, d->num_actions);
-    auto is_float = [](int32_t t) { return t == SGW_POLICY_F32 || t == SGW_POLICY_F64; };
-    if (!is_float(d->dist_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown dist_type %d", d->dist_type);
+    if (!is_float_type(d->dist_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown dist_type %d", d->dist_type);
     if (d->mode != SGW_POLICY_PROBS && d->mode != SGW_POLICY_LOGITS) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown mode %d", d->mode);
-    if (!is_float(d->value_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown value_type %d", d->value_type);
+    if (!is_float_type(d->value_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown value_type %d", d->value_type);
     if (d->action_type != SGW_PPO_ACT_I64 && d->action_type != SGW_PPO_ACT_U8) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown action_type %d", d->action_type);
-    if (!is_float(d->returns_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown returns_type %d", d->returns_type);
+    if (!is_float_type(d->returns_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: unknown returns_type %d", d->returns_type);
     if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "sgw_ppo_loss: reserved fields must be 0");
     if (!(d->eps_clip >= 0.0) || !std::isfinite(d->eps_clip)) return fail(SGW_EINVAL, "sgw_ppo_loss: eps_clip = %g must be finite and not negative", d->eps_clip);
-    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-    auto mask = [](int32_t t) { return (uintptr_t)(t == SGW_POLICY_F64 ? 7 : 3); };
-    if ((at(d->dist) | at(d->out_grad_dist)) & mask(d->dist_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: dist / out_grad_dist is not aligned to its element type");
-    if ((at(d->values) | at(d->out_grad_values)) & mask(d->value_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: values / out_grad_values is not aligned to its element type");
-    if (at(d->returns) & mask(d->returns_type)) return fail(SGW_EINVAL, "sgw_ppo_loss: returns is not aligned to its element type");
-    if (at(d->old_log_probs) & 3) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned float32 pointer (old_log_probs)");
-    if (d->action_type == SGW_PPO_ACT_I64 && (at(d->actions) & 7)) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned int64 pointer (actions)");
-    if ((at(d->out_row_terms) | at(d->out_terms) | at(d->workspace)) & 7) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned float64 pointer (out_row_terms, out_terms or workspace)");
+    if (misaligned(float_mask(d->dist_type), {d->dist, d->out_grad_dist})) return fail(SGW_EINVAL, "sgw_ppo_loss: dist / out_grad_dist is not aligned to its element type");
+    if (misaligned(float_mask(d->value_type), {d->values, d->out_grad_values})) return fail(SGW_EINVAL, "sgw_ppo_loss: values / out_grad_values is not aligned to its element type");
+    if (misaligned(float_mask(d->returns_type), {d->returns})) return fail(SGW_EINVAL, "sgw_ppo_loss: returns is not aligned to its element type");
+    if (misaligned(3, {d->old_log_probs})) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned float32 pointer (old_log_probs)");
+    if (d->action_type == SGW_PPO_ACT_I64 && misaligned(7, {d->actions})) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned int64 pointer (actions)");
+    if (misaligned(7, {d->out_row_terms, d->out_terms, d->workspace})) return fail(SGW_EINVAL, "sgw_ppo_loss: misaligned float64 pointer (out_row_terms, out_terms or workspace)");
     if (d->n > INT64_MAX / 8 / d->row_stride || d->n > INT64_MAX / 32) return fail(SGW_EINVAL, "sgw_ppo_loss: n = %lld rows of stride %lld do not fit 64-bit offsets", (long long)d->n, (long long)d->row_stride);
     const unsigned blocks = (unsigned)ppo_loss_blocks(d->n);
-    const int64_t need = (int64_t)blocks * 3 * (int64_t)sizeof(double);
-    if (need > 0 && (!d->workspace || d->workspace_bytes < need))
-        return fail(SGW_EINVAL, "sgw_ppo_loss: needs a workspace of %lld bytes (sgw_ppo_loss_workspace_bytes); got %lld", (long long)need, d->workspace ? (long long)d->workspace_bytes : 0ll);
+    if (int rc = workspace_short("sgw_ppo_loss", d->workspace, d->workspace_bytes, (int64_t)blocks * 3 * (int64_t)sizeof(double))) return rc;
     if (d->n == 0) return SGW_OK;
     PpoLossParams p{};
     p.dist = d->dist; p.values = d->values; p.actions = d->actions; p.old_lp = d->old_log_probs; p.returns = d->returns;
@@ -1476,8 +1482,7 @@ int sgw_ppo_loss(const sgw_ppo_loss_desc* d, void* stream) {
     if (f64) launch_ppo_loss<true>(p, vec, blocks, s);
     else launch_ppo_loss<false>(p, vec, blocks, s);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ppo_loss_merge_kernel, dim3(1), dim3(kBlock), 0, s, p);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(ppo_loss_merge_kernel, 1, s, p);
     return SGW_OK;
 }
 
@@ -1496,23 +1501,20 @@ int sgw_iqn_loss(const sgw_iqn_loss_desc* d, void* stream) {
     if (d->num_quantiles < 1 || d->num_quantiles > kIqnMaxQuantiles) return fail(SGW_EINVAL, "sgw_iqn_loss: num_quantiles = %d outside [1, %d]", d->num_quantiles, kIqnMaxQuantiles);
     if (d->num_actions < 1 || d->num_actions > kIqnMaxActions) return fail(SGW_EINVAL, "sgw_iqn_loss: num_actions = %d outside [1, %d]", d->num_actions, kIqnMaxActions);
     if (d->action_type != SGW_PPO_ACT_I64 && d->action_type != SGW_PPO_ACT_U8) return fail(SGW_EINVAL, "sgw_iqn_loss: unknown action_type %d", d->action_type);
-    if (d->valid_type != SGW_POLICY_F32 && d->valid_type != SGW_POLICY_F64) return fail(SGW_EINVAL, "sgw_iqn_loss: unknown valid_type %d", d->valid_type);
+    if (!is_float_type(d->valid_type)) return fail(SGW_EINVAL, "sgw_iqn_loss: unknown valid_type %d", d->valid_type);
     if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "sgw_iqn_loss: reserved fields must be 0");
     if (!std::isfinite(d->discount)) return fail(SGW_EINVAL, "sgw_iqn_loss: discount = %g must be finite", d->discount);
-    auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-    if ((at(d->q_next_local) | at(d->q_next_target) | at(d->q_expected) | at(d->taus) | at(d->rewards) | at(d->dones) | at(d->out_grad_expected) | at(d->out_td_error)) & 3)
+    if (misaligned(3, {d->q_next_local, d->q_next_target, d->q_expected, d->taus, d->rewards, d->dones, d->out_grad_expected, d->out_td_error}))
         return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned float32 pointer (q_next_local, q_next_target, q_expected, taus, rewards, dones, out_grad_expected or out_td_error)");
-    if (d->action_type == SGW_PPO_ACT_I64 && (at(d->actions) & 7)) return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned int64 pointer (actions)");
-    if (at(d->valid) & (d->valid_type == SGW_POLICY_F64 ? 7 : 3)) return fail(SGW_EINVAL, "sgw_iqn_loss: valid is not aligned to its element type");
-    if ((at(d->out_terms) | at(d->out_next_actions) | at(d->out_row_terms) | at(d->workspace)) & 7)
+    if (d->action_type == SGW_PPO_ACT_I64 && misaligned(7, {d->actions})) return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned int64 pointer (actions)");
+    if (misaligned(float_mask(d->valid_type), {d->valid})) return fail(SGW_EINVAL, "sgw_iqn_loss: valid is not aligned to its element type");
+    if (misaligned(7, {d->out_terms, d->out_next_actions, d->out_row_terms, d->workspace}))
         return fail(SGW_EINVAL, "sgw_iqn_loss: misaligned 8-byte pointer (out_terms, out_next_actions, out_row_terms or workspace)");
     const int64_t widest = (int64_t)d->num_quantiles * std::max(d->num_actions, d->num_quantiles);
     if (d->n > INT64_MAX / 8 / widest || d->n > INT64_MAX / 32)
         return fail(SGW_EINVAL, "sgw_iqn_loss: n = %lld rows of %d x %d do not fit 64-bit offsets", (long long)d->n, d->num_quantiles, d->num_actions);
     const unsigned blocks = (unsigned)iqn_loss_blocks(d->n, d->num_quantiles);
-    const int64_t need = (int64_t)blocks * (int64_t)sizeof(double);
-    if (need > 0 && (!d->workspace || d->workspace_bytes < need))
-        return fail(SGW_EINVAL, "sgw_iqn_loss: needs a workspace of %lld bytes (sgw_iqn_loss_workspace_bytes); got %lld", (long long)need, d->workspace ? (long long)d->workspace_bytes : 0ll);
+    if (int rc = workspace_short("sgw_iqn_loss", d->workspace, d->workspace_bytes, (int64_t)blocks * (int64_t)sizeof(double))) return rc;
     if (d->n == 0) return SGW_OK;
     IqnLossParams p{};
     p.q_next_local = d->q_next_local; p.q_next_target = d->q_next_target; p.q_expected = d->q_expected; p.taus = d->taus;
@@ -1529,8 +1531,7 @@ int sgw_iqn_loss(const sgw_iqn_loss_desc* d, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     launch_iqn_loss(p, vec, blocks, s);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(iqn_loss_merge_kernel, dim3(1), dim3(kBlock), 0, s, p);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(iqn_loss_merge_kernel, 1, s, p);
     return SGW_OK;
 }
 

@@ -139,44 +139,28 @@ constexpr int kRedBlocks = 256;
 
 // stage 1: block b sums elements b*256+t, stride 65536, in a fixed order
 __global__ __launch_bounds__(kBlock) void reduce_stage1(const double* __restrict__ x, int64_t n, double* __restrict__ part) {
-    __shared__ double s[kBlock], s2[kBlock];
+    __shared__ double red[2][kBlock];
     double a = 0.0, a2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)kRedBlocks * kBlock) {
         const double v = x[i];
         a += v;
         a2 += v * v;
     }
-    s[threadIdx.x] = a;
-    s2[threadIdx.x] = a2;
-    __syncthreads();
-    for (int k = kBlock / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            s[threadIdx.x] += s[threadIdx.x + k];
-            s2[threadIdx.x] += s2[threadIdx.x + k];
-        }
-        __syncthreads();
-    }
+    const double sums[2] = {a, a2};
+    block_tree<2>(sums, red, TreeSum{});
     if (threadIdx.x == 0) {
-        part[blockIdx.x] = s[0];
-        part[kRedBlocks + blockIdx.x] = s2[0];
+        part[blockIdx.x] = red[0][0];
+        part[kRedBlocks + blockIdx.x] = red[1][0];
     }
 }
 
 __global__ __launch_bounds__(kBlock) void reduce_stage2(const double* __restrict__ part, int64_t n, double* __restrict__ out) {
-    __shared__ double s[kBlock], s2[kBlock];
-    s[threadIdx.x] = part[threadIdx.x];
-    s2[threadIdx.x] = part[kRedBlocks + threadIdx.x];
-    __syncthreads();
-    for (int k = kBlock / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            s[threadIdx.x] += s[threadIdx.x + k];
-            s2[threadIdx.x] += s2[threadIdx.x + k];
-        }
-        __syncthreads();
-    }
+    __shared__ double red[2][kBlock];
+    const double sums[2] = {part[threadIdx.x], part[kRedBlocks + threadIdx.x]};
+    block_tree<2>(sums, red, TreeSum{});
     if (threadIdx.x == 0) {
-        out[0] = s[0];
-        out[1] = s2[0];
+        out[0] = red[0][0];
+        out[1] = red[1][0];
         out[2] = (double)n;
         out[3] = 0.0;
     }
