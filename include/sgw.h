@@ -870,6 +870,90 @@ int sgw_iqn_loss(const sgw_iqn_loss_desc* desc, void* stream);
  * outside 1..64. */
 int64_t sgw_iqn_loss_workspace_bytes(int64_t n, int32_t num_quantiles);
 
+/* ---- Adam, gradient clipping and the soft update (sorrel/models/pytorch/iqn.py:405-410: clip_grad_norm_(local.parameters(), 1),
+ * optimizer.step(), soft_update(); ppo.py:283-285: Adam over two parameter groups in float64 -- what the reference runs after
+ * loss.backward(), some eighty small launches on device tensors; on the device in two launches, one when nothing is clipped) ----
+ * One call handles num_tensors = T (1..4096) tensors of ONE dtype (SGW_POLICY_F32 / _F64).  Tensor k has a record: param, grad (NULL:
+ * the tensor is skipped entirely, as torch skips p.grad is None), exp_avg = m, exp_avg_sq = v, target (NULL: no soft update), numel and
+ * a learning rate of its own (so PPO's two groups are one call).  beta1, beta2, eps and tau are call-wide.  No weight decay, amsgrad or
+ * maximize.  Arithmetic is done in the tensors' dtype, written F(x) for a double rounded to it; every operation is rounded on its own
+ * except the two marked fma, which are single fused multiply-adds -- the order that reproduces torch.optim.Adam(foreach=False) on the CPU.
+ *   bias       by value (step >= 1, step_state NULL), in double, torch's _single_tensor_adam for a Python-float step:
+ *                  bc1 = 1 - pow(beta1, (double)step);   bc2 = 1 - pow(beta2, (double)step);
+ *                  step_size = lr / bc1;                 (per tensor)
+ *                  bc2_sqrt = pow(bc2, 0.5);             (torch writes bias_correction2 ** 0.5: libm's pow, not sqrt)
+ *              from the device (step_state given, step == 0): the first launch's block 0 advances the state, step += 1,
+ *              beta1_pow *= beta1, beta2_pow *= beta2 in double -- RUNNING PRODUCTS, not pow --; the second launch reads it:
+ *              bc1 = 1 - beta1_pow; bc2 = 1 - beta2_pow; step_size = lr / bc1; bc2_sqrt = sqrt(bc2).  A fresh state is {0, 1.0, 1.0}.
+ *   clip       SGW_ADAM_CLIP_NONE: g = grad.
+ *              SGW_ADAM_CLIP_NORM: a chunk is SGW_ADAM_CHUNK = 4096 consecutive elements of one tensor (the last one shorter).  Lane t
+ *              of 256 owns the elements 4 (t + 256 r) + e of its chunk, r = 0..3, e = 0..3, and adds (double)grad * (double)grad of
+ *              those that exist serially in that order; the 256 sums are merged by the halving tree (slot t += slot t + s,
+ *              s = 128 .. 1): S_chunk.  A tensor's chunks are added serially in chunk order: S_k (0 for a skipped or empty tensor).
+ *              Lane i adds S_i, S_(i + 256), ... serially and the same tree merges the lanes: S.  norm = sqrt(S) in double;
+ *              c = F(max_norm) / (F(norm) + F(1e-6)); c > 1 ? 1 : c (a NaN stays a NaN and propagates, as torch's does).
+ *              No atomics: the order depends on indices alone, two runs give the same bits.
+ *              SGW_ADAM_CLIP_COEF: c is read from clip_coef, a device scalar of the tensors' dtype (after an all-reduce, say).
+ *              In both: g = grad * c, always multiplied, as clip_grad_norm_ does.
+ *   moments    m' = fma(F(1 - beta1), g - m, m)                     (fma; torch's lerp_ for a weight below 0.5: 1 - beta1 >= 0.5 is refused)
+ *              v' = fma(F(1 - beta2) * g, g, v * F(beta2))          (fma)
+ *   param      denom = F(sqrt(v') / F(bc2_sqrt)) + F(eps);   p' = p + (F(-step_size) * m') / denom
+ *   target     t' = F(tau) * p' + F(1.0 - tau) * t                  (three roundings; only where a target is given)
+ * grad is read only, unless SGW_ADAM_ZERO_GRADS is set: then +0 is stored after the read.  The clipped gradient is NOT written back
+ * (after the reference's lines p.grad holds it).  out_norm, if given, receives {norm, c}: norm is NaN unless SGW_ADAM_CLIP_NORM, c is 1
+ * for SGW_ADAM_CLIP_NONE.  A tensor of numel 0 is legal and untouched.  Tensors must not overlap.
+ * The tensor table lies in device memory so that a call can be recorded; planning and stepping are therefore two calls.
+ * sgw_adam_plan validates T records on the host and writes the host image of the table: T device records and the chunk map.  The caller
+ * copies info->image_bytes bytes of it to the device (8-byte aligned) and passes that, info->num_chunks and a workspace of
+ * info->workspace_bytes bytes (8-byte aligned; read and written by SGW_ADAM_CLIP_NORM only) to sgw_adam_step.  Needs no engine;
+ * asynchronous on `stream`; no host synchronisation.  Everything the host can see -- a NULL required pointer (records, host_image, info;
+ * param always, exp_avg and exp_avg_sq where grad is given; plan; clip_coef for SGW_ADAM_CLIP_COEF), a pointer not aligned to its element
+ * type, numel < 0, T outside 1..4096, 2^31 chunks or more, a beta outside [0, 1), 1 - beta1 >= 0.5, a non-finite lr, max_norm, beta, eps
+ * or tau, step < 1 without a step_state or != 0 with one, a short image, plan or workspace, an unknown dtype, clip_mode or flag, a
+ * non-zero reserved field -- is SGW_EINVAL with the reason in sgw_last_error(), before anything is launched. */
+#define SGW_ADAM_CLIP_NONE 0
+#define SGW_ADAM_CLIP_NORM 1
+#define SGW_ADAM_CLIP_COEF 2
+#define SGW_ADAM_ZERO_GRADS 1    /* flags: store +0 to every gradient after reading it */
+#define SGW_ADAM_MAX_TENSORS 4096
+#define SGW_ADAM_CHUNK 4096
+typedef struct sgw_adam_tensor {
+    void* param;
+    void* grad;                  /* NULL: skipped entirely */
+    void* exp_avg;
+    void* exp_avg_sq;
+    void* target;                /* NULL: no soft update */
+    int64_t numel;
+    double lr;
+    int64_t reserved;            /* reserved: 0 */
+} sgw_adam_tensor;
+typedef struct sgw_adam_plan_info {
+    int64_t num_chunks, workspace_bytes, image_bytes, total_numel;     /* total_numel: of the tensors that are not skipped */
+} sgw_adam_plan_info;
+typedef struct sgw_adam_step_state {
+    int64_t step;
+    double beta1_pow, beta2_pow;
+} sgw_adam_step_state;
+typedef struct sgw_adam_step_desc {
+    const void* plan;            /* the uploaded image of sgw_adam_plan */
+    int64_t plan_bytes;
+    const void* clip_coef;       /* SGW_ADAM_CLIP_COEF: one element of dtype */
+    sgw_adam_step_state* step_state;     /* device; or NULL: `step` counts */
+    double* out_norm;            /* [2] = norm, c; or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t num_tensors, num_chunks;
+    int64_t step;
+    double max_norm, beta1, beta2, eps, tau;
+    int32_t dtype, clip_mode, flags;
+    int32_t reserved0, reserved1;        /* reserved: 0 */
+} sgw_adam_step_desc;
+/* Bytes that hold the image of any T tensors of total_numel elements in all (an upper bound); a negative code for T outside 1..4096 or
+ * total_numel < 0. */
+int64_t sgw_adam_plan_bytes(int64_t num_tensors, int64_t total_numel);
+int sgw_adam_plan(const sgw_adam_tensor* records, int64_t num_tensors, int32_t dtype, void* host_image, int64_t image_bytes, sgw_adam_plan_info* info);
+int sgw_adam_step(const sgw_adam_step_desc* desc, void* stream);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

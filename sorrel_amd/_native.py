@@ -37,6 +37,9 @@ POLICY_PROBS, POLICY_LOGITS = 0, 1
 POLICY_MAX_ACTIONS = 256
 PPO_ACT_I64, PPO_ACT_U8 = 0, 1
 IQN_MAX_QUANTILES = 64
+ADAM_CLIP_NONE, ADAM_CLIP_NORM, ADAM_CLIP_COEF = 0, 1, 2
+ADAM_ZERO_GRADS = 1
+ADAM_MAX_TENSORS, ADAM_CHUNK = 4096, 4096
 POLICY_INVALID_ACTION = 255  # the action of a row torch's Categorical would raise for (its log-probability and entropy are NaN)
 
 
@@ -209,6 +212,46 @@ class SgwIqnLossDesc(C.Structure):
     ]
 
 
+class SgwAdamTensor(C.Structure):
+    """Mirror of ``struct sgw_adam_tensor`` (include/sgw.h): one tensor of an ``sgw_adam_plan`` call; layout checked by tests/test_adam_step_cpu.py."""
+
+    _fields_ = [
+        ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("target", C.c_void_p),
+        ("numel", C.c_int64),
+        ("lr", C.c_double),
+        ("reserved", C.c_int64),
+    ]
+
+
+class SgwAdamPlanInfo(C.Structure):
+    """Mirror of ``struct sgw_adam_plan_info``."""
+
+    _fields_ = [("num_chunks", C.c_int64), ("workspace_bytes", C.c_int64), ("image_bytes", C.c_int64), ("total_numel", C.c_int64)]
+
+
+class SgwAdamStepState(C.Structure):
+    """Mirror of ``struct sgw_adam_step_state``: the device's step count and the running products of the betas."""
+
+    _fields_ = [("step", C.c_int64), ("beta1_pow", C.c_double), ("beta2_pow", C.c_double)]
+
+
+class SgwAdamStepDesc(C.Structure):
+    """Mirror of ``struct sgw_adam_step_desc``: one ``sgw_adam_step`` call."""
+
+    _fields_ = [
+        ("plan", C.c_void_p),
+        ("plan_bytes", C.c_int64),
+        ("clip_coef", C.c_void_p), ("step_state", C.c_void_p), ("out_norm", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("num_tensors", C.c_int64), ("num_chunks", C.c_int64),
+        ("step", C.c_int64),
+        ("max_norm", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("tau", C.c_double),
+        ("dtype", C.c_int32), ("clip_mode", C.c_int32), ("flags", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -224,6 +267,7 @@ EXPORTS = (
     "sgw_policy_sample", "sgw_turn_policy_sample",
     "sgw_ppo_loss", "sgw_ppo_loss_workspace_bytes",
     "sgw_iqn_loss", "sgw_iqn_loss_workspace_bytes",
+    "sgw_adam_plan_bytes", "sgw_adam_plan", "sgw_adam_step",
     "sgw_last_error", "sgw_version",
 )
 
@@ -381,6 +425,12 @@ def load():
     lib.sgw_iqn_loss.restype = C.c_int
     lib.sgw_iqn_loss_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.sgw_iqn_loss_workspace_bytes.restype = C.c_int64
+    lib.sgw_adam_plan_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.sgw_adam_plan_bytes.restype = C.c_int64
+    lib.sgw_adam_plan.argtypes = [C.POINTER(SgwAdamTensor), C.c_int64, C.c_int32, vp, C.c_int64, C.POINTER(SgwAdamPlanInfo)]
+    lib.sgw_adam_plan.restype = C.c_int
+    lib.sgw_adam_step.argtypes = [C.POINTER(SgwAdamStepDesc), vp]
+    lib.sgw_adam_step.restype = C.c_int
     lib.sgw_last_error.argtypes = []
     lib.sgw_last_error.restype = C.c_char_p
     lib.sgw_version.argtypes = []

@@ -77,6 +77,7 @@ namespace {
 #include "policy.h"
 #include "ppo_loss.h"
 #include "iqn_loss.h"
+#include "adam_step.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -98,7 +99,7 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(SGW_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss) ask of their arguments
+// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss, sgw_adam_step) ask of their arguments
 inline uintptr_t at(const void* q) { return reinterpret_cast<uintptr_t>(q); }
 // is any of these pointers off the alignment `mask` + 1?  (NULL, an optional argument or one of another type, is aligned to everything)
 inline bool misaligned(const uintptr_t mask, std::initializer_list<const void*> ptrs) {
@@ -1532,6 +1533,108 @@ int sgw_iqn_loss(const sgw_iqn_loss_desc* d, void* stream) {
     launch_iqn_loss(p, vec, blocks, s);
     HIP_TRY(hipGetLastError());
     LAUNCH_TRY(iqn_loss_merge_kernel, 1, s, p);
+    return SGW_OK;
+}
+
+// ---------------------------------------------------------------- Adam, clipping and the soft update (adam_step.h)
+int64_t sgw_adam_plan_bytes(int64_t num_tensors, int64_t total_numel) {
+    if (num_tensors < 1 || num_tensors > kAdamMaxTensors) return fail(SGW_EINVAL, "sgw_adam_plan_bytes: num_tensors = %lld outside [1, %d]", (long long)num_tensors, kAdamMaxTensors);
+    if (total_numel < 0) return fail(SGW_EINVAL, "sgw_adam_plan_bytes: total_numel = %lld", (long long)total_numel);
+    // (every tensor ends in at most one chunk that is not full)
+    return num_tensors * (int64_t)sizeof(AdamRec) + (total_numel / kAdamChunk + num_tensors) * (int64_t)sizeof(AdamChunk);
+}
+
+int sgw_adam_plan(const sgw_adam_tensor* records, int64_t T, int32_t dtype, void* host_image, int64_t image_bytes, sgw_adam_plan_info* info) {
+    if (!records || !host_image || !info) return fail(SGW_EINVAL, "sgw_adam_plan: records, host_image and info must not be NULL");
+    if (T < 1 || T > kAdamMaxTensors) return fail(SGW_EINVAL, "sgw_adam_plan: num_tensors = %lld outside [1, %d]", (long long)T, kAdamMaxTensors);
+    if (!is_float_type(dtype)) return fail(SGW_EINVAL, "sgw_adam_plan: unknown dtype %d", dtype);
+    if (misaligned(7, {host_image})) return fail(SGW_EINVAL, "sgw_adam_plan: misaligned 8-byte pointer (host_image)");
+    int64_t chunks = 0, total = 0;
+    for (int64_t k = 0; k < T; ++k) {
+        const sgw_adam_tensor& r = records[k];
+        if (!r.param) return fail(SGW_EINVAL, "sgw_adam_plan: tensor %lld: param must not be NULL", (long long)k);
+        if (r.grad && (!r.exp_avg || !r.exp_avg_sq)) return fail(SGW_EINVAL, "sgw_adam_plan: tensor %lld: exp_avg and exp_avg_sq must not be NULL where grad is given", (long long)k);
+        if (r.numel < 0) return fail(SGW_EINVAL, "sgw_adam_plan: tensor %lld: numel = %lld", (long long)k, (long long)r.numel);
+        if (!std::isfinite(r.lr)) return fail(SGW_EINVAL, "sgw_adam_plan: tensor %lld: lr = %g must be finite", (long long)k, r.lr);
+        if (r.reserved) return fail(SGW_EINVAL, "sgw_adam_plan: tensor %lld: reserved fields must be 0", (long long)k);
+        if (misaligned(float_mask(dtype), {r.param, r.grad, r.exp_avg, r.exp_avg_sq, r.target}))
+            return fail(SGW_EINVAL, "sgw_adam_plan: tensor %lld: a pointer is not aligned to its element type", (long long)k);
+        if (r.grad && r.numel > 0) {
+            chunks += adam_chunks(r.numel);
+            total += r.numel;
+            if (chunks > INT32_MAX) return fail(SGW_EINVAL, "sgw_adam_plan: 2^31 chunks or more");
+        }
+    }
+    const int64_t need = T * (int64_t)sizeof(AdamRec) + chunks * (int64_t)sizeof(AdamChunk);
+    if (image_bytes < need) return fail(SGW_EINVAL, "sgw_adam_plan: the image needs %lld bytes (sgw_adam_plan_bytes); got %lld", (long long)need, (long long)image_bytes);
+    AdamRec* recs = static_cast<AdamRec*>(host_image);
+    AdamChunk* map = reinterpret_cast<AdamChunk*>(recs + T);
+    int64_t at_chunk = 0;
+    for (int64_t k = 0; k < T; ++k) {
+        const sgw_adam_tensor& r = records[k];
+        AdamRec o{};
+        o.p = r.param; o.g = r.grad; o.m = r.exp_avg; o.v = r.exp_avg_sq; o.t = r.target;
+        o.numel = r.numel; o.lr = r.lr;
+        o.first_chunk = (int32_t)at_chunk;
+        o.flags = misaligned(15, {r.param, r.grad, r.exp_avg, r.exp_avg_sq, r.target}) ? 0 : kAdamVec;
+        recs[k] = o;
+        const int64_t nc = r.grad && r.numel > 0 ? adam_chunks(r.numel) : 0;
+        for (int64_t j = 0; j < nc; ++j) map[at_chunk + j] = AdamChunk{(int32_t)k, (int32_t)j};
+        at_chunk += nc;
+    }
+    info->num_chunks = chunks;
+    info->workspace_bytes = chunks * (int64_t)sizeof(double);
+    info->image_bytes = need;
+    info->total_numel = total;
+    return SGW_OK;
+}
+
+int sgw_adam_step(const sgw_adam_step_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_adam_step: desc is NULL");
+    if (!d->plan) return fail(SGW_EINVAL, "sgw_adam_step: plan must not be NULL");
+    if (d->num_tensors < 1 || d->num_tensors > kAdamMaxTensors) return fail(SGW_EINVAL, "sgw_adam_step: num_tensors = %lld outside [1, %d]", (long long)d->num_tensors, kAdamMaxTensors);
+    if (d->num_chunks < 0 || d->num_chunks > INT32_MAX) return fail(SGW_EINVAL, "sgw_adam_step: num_chunks = %lld outside [0, 2^31)", (long long)d->num_chunks);
+    if (!is_float_type(d->dtype)) return fail(SGW_EINVAL, "sgw_adam_step: unknown dtype %d", d->dtype);
+    if (d->clip_mode != SGW_ADAM_CLIP_NONE && d->clip_mode != SGW_ADAM_CLIP_NORM && d->clip_mode != SGW_ADAM_CLIP_COEF) return fail(SGW_EINVAL, "sgw_adam_step: unknown clip_mode %d", d->clip_mode);
+    if (d->flags & ~SGW_ADAM_ZERO_GRADS) return fail(SGW_EINVAL, "sgw_adam_step: unknown flags 0x%x", (unsigned)d->flags);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "sgw_adam_step: reserved fields must be 0");
+    if (!std::isfinite(d->max_norm) || !std::isfinite(d->beta1) || !std::isfinite(d->beta2) || !std::isfinite(d->eps) || !std::isfinite(d->tau))
+        return fail(SGW_EINVAL, "sgw_adam_step: max_norm = %g, beta1 = %g, beta2 = %g, eps = %g and tau = %g must be finite", d->max_norm, d->beta1, d->beta2, d->eps, d->tau);
+    if (d->beta1 < 0.0 || d->beta1 >= 1.0 || d->beta2 < 0.0 || d->beta2 >= 1.0) return fail(SGW_EINVAL, "sgw_adam_step: beta1 = %g, beta2 = %g outside [0, 1)", d->beta1, d->beta2);
+    if (1.0 - d->beta1 >= 0.5) return fail(SGW_EINVAL, "sgw_adam_step: 1 - beta1 = %g must be below 0.5 (the lerp's other branch is out of scope)", 1.0 - d->beta1);
+    if (d->step_state ? d->step != 0 : d->step < 1) return fail(SGW_EINVAL, "sgw_adam_step: step = %lld (>= 1 without a step_state, 0 with one)", (long long)d->step);
+    if (d->clip_mode == SGW_ADAM_CLIP_COEF && !d->clip_coef) return fail(SGW_EINVAL, "sgw_adam_step: SGW_ADAM_CLIP_COEF needs clip_coef");
+    if (misaligned(float_mask(d->dtype), {d->clip_coef})) return fail(SGW_EINVAL, "sgw_adam_step: clip_coef is not aligned to its element type");
+    if (misaligned(7, {d->plan, d->step_state, d->out_norm, d->workspace})) return fail(SGW_EINVAL, "sgw_adam_step: misaligned 8-byte pointer (plan, step_state, out_norm or workspace)");
+    const int64_t image = d->num_tensors * (int64_t)sizeof(AdamRec) + d->num_chunks * (int64_t)sizeof(AdamChunk);
+    if (d->plan_bytes < image) return fail(SGW_EINVAL, "sgw_adam_step: a plan of %lld tensors and %lld chunks has %lld bytes; got %lld", (long long)d->num_tensors, (long long)d->num_chunks, (long long)image, (long long)d->plan_bytes);
+    const bool norm = d->clip_mode == SGW_ADAM_CLIP_NORM;
+    if (norm)
+        if (int rc = workspace_short("sgw_adam_step", d->workspace, d->workspace_bytes, d->num_chunks * (int64_t)sizeof(double), " SGW_ADAM_CLIP_NORM")) return rc;
+    AdamParams p{};
+    p.recs = static_cast<const AdamRec*>(d->plan);
+    p.map = reinterpret_cast<const AdamChunk*>(p.recs + d->num_tensors);
+    p.partials = static_cast<double*>(d->workspace);
+    p.coef = d->clip_coef; p.state = d->step_state; p.out_norm = d->out_norm;
+    p.max_norm = d->max_norm; p.beta1 = d->beta1; p.beta2 = d->beta2; p.omb1 = 1.0 - d->beta1; p.omb2 = 1.0 - d->beta2;
+    p.eps = d->eps; p.tau = d->tau; p.omtau = 1.0 - d->tau;
+    if (!d->step_state) {
+        p.bc1 = 1.0 - std::pow(d->beta1, (double)d->step);
+        p.bc2_sqrt = std::pow(1.0 - std::pow(d->beta2, (double)d->step), 0.5);
+    }
+    p.T = (int32_t)d->num_tensors; p.nchunks = (int32_t)d->num_chunks; p.zero = d->flags & SGW_ADAM_ZERO_GRADS;
+    const bool f64 = d->dtype == SGW_POLICY_F64;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (d->step_state || (norm && d->num_chunks > 0)) {
+        const unsigned blocks = norm ? adam_blocks(d->num_chunks) : 1u;
+        if (f64) hipLaunchKernelGGL(adam_norm_kernel<double>, dim3(blocks), dim3(kBlock), 0, s, p, (int)norm);
+        else hipLaunchKernelGGL(adam_norm_kernel<float>, dim3(blocks), dim3(kBlock), 0, s, p, (int)norm);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d->num_chunks == 0 && !d->out_norm) return SGW_OK;
+    if (f64) launch_adam_apply<double>(p, d->clip_mode, adam_blocks(d->num_chunks), s);
+    else launch_adam_apply<float>(p, d->clip_mode, adam_blocks(d->num_chunks), s);
+    HIP_TRY(hipGetLastError());
     return SGW_OK;
 }
 

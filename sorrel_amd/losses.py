@@ -22,6 +22,7 @@ outputs and ``loss.backward()``) has the same three forms -- ``iqn_loss_terms`` 
     q_expected, taus = local(states, n_quantiles)
     loss = iqn_loss(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, GAMMA ** n_step)
     optimizer.zero_grad(); loss.backward(); clip_grad_norm_(local.parameters(), 1); optimizer.step()
+    # or, with optimizer = sorrel_amd.optim.FusedAdam(local.parameters(), max_grad_norm=1, target_params=target.parameters(), tau=TAU): optimizer.step() alone
 """
 from __future__ import annotations
 
