@@ -954,6 +954,83 @@ int64_t sgw_adam_plan_bytes(int64_t num_tensors, int64_t total_numel);
 int sgw_adam_plan(const sgw_adam_tensor* records, int64_t num_tensors, int32_t dtype, void* host_image, int64_t image_bytes, sgw_adam_plan_info* info);
 int sgw_adam_step(const sgw_adam_step_desc* desc, void* stream);
 
+/* ---- IQN's network forward (sorrel/models/pytorch/iqn.py:110-167: IQN.forward and get_qvalues, with layers.py's NoisyLinear -- the
+ * head layer, the cosine embedding of every quantile, their product, the noisy layer, the dueling head and the mean over the
+ * quantiles; a dozen torch launches whose [n N][L] intermediates pass through memory; on the device in two launches) ----
+ * Row b of n has in_features = D state elements (float32 or uint8: state_type; uint8 is widened exactly), rows state_stride elements
+ * apart.  layer_size = L (1..256), num_quantiles = N (1..64), num_actions = A (1..64), n_cos = 64.  The ten weight tensors are
+ * contiguous float32 in nn.Linear's [out][in] layout: w_head[L][D], b_head[L], w_cos[L][64], b_cos[L], w_ff[L][L], b_ff[L],
+ * w_adv[A][L], b_adv[A], w_val[L], b_val[1].  They are the EFFECTIVE weights: a noisy layer in training mode is weight + sigma * epsilon,
+ * formed by the caller; the call knows nothing about noise.  No gradient: this is the forward of acting and of the two next_states calls.
+ * All arithmetic is float32.  chain_k(x_k, w_k; b) is ONE fused multiply-add chain over k ascending that starts at the bias,
+ * fmaf(x_K-1, w_K-1, ... fmaf(x_1, w_1, fmaf(x_0, w_0, b))) -- no split sums -- so a row's result depends on nothing but the row:
+ * not on the batch, on the tile the row lands in, or on the grid.  relu(x) = x > 0 ? x : (x != x ? x : +0): a NaN goes through.
+ *   taus       given (taus != NULL: float32 [n][N]), or drawn: row k is keyed as (env, agent) = (idx[k] % num_envs, idx[k] / num_envs), or
+ *              with idx == NULL as (k % num_envs, agent0 + k / num_envs) -- sgw_policy_sample's keys --;
+ *              u = Philox4x32-10(ctr = {(agent << 4) | (q >> 2), turn, first_env + env, epoch << 4 | SGW_STREAM_TAU},
+ *              key = {seed lo, seed hi})[q & 3];  tau_q = (float)(u >> 8) * 2^-24, in [0, 1).  Keyed, not consumed: a function of
+ *              (seed, env, epoch, turn, agent, quantile) alone.  A row whose idx entry names no (env, agent) pair gets NaN taus.
+ *   head       h_l = relu(chain_k(x_k, w_head[l][k]; b_head[l]))
+ *   embedding  arg_qi = tau_q * (float)(M_PI * i), i = 1..64: the constant is the double product rounded once (torch.FloatTensor([np.pi * i])),
+ *              the product is float32;  c_qi = cosf(arg_qi), the device library's full-precision cosf;
+ *              e_ql = relu(chain_i(c_qi, w_cos[l][i - 1]; b_cos[l]))
+ *   product    z_ql = h_l * e_ql, rounded
+ *   noisy      y_ql = relu(chain_k(z_qk, w_ff[l][k]; b_ff[l]))
+ *   dueling    adv_qa = chain_k(y_qk, w_adv[a][k]; b_adv[a]);  val_q = chain_k(y_qk, w_val[k]; b_val[0]);
+ *              mean_q = (((adv_q0 + adv_q1) + ...)) / (float)A, summed serially;  quant_qa = (val_q + adv_qa) - mean_q
+ *   qvalues    qvalue_a = (((quant_0a + quant_1a) + ...)) / (float)N, summed serially: sgw_iqn_loss's m_a, and what SGW_ACT_QF32 and
+ *              sgw_choose_actions take (argmax and exploration stay theirs)
+ * Outputs, all contiguous float32 and each optional (NULL), but one of out_qvalues and out_quantiles must be given: out_qvalues [n][A],
+ * out_quantiles [n][N][A], out_taus [n][N], out_cos [n][N][64] (c_qi: everything behind the one library call can be restated from it
+ * bit for bit).  workspace: sgw_iqn_forward_workspace_bytes(n, layer_size) bytes, 4-byte aligned, overwritten: h [n][L] between the
+ * head launch (rows as the GEMM's M, K = D) and the quantile launch (M = n N).  Nothing of size n N L reaches memory.  No atomics: two
+ * runs give the same bits.  Needs no engine; all pointers are device pointers.  Asynchronous on `stream`; everything the host can
+ * see -- a NULL required pointer, neither out_qvalues nor out_quantiles, an unknown state_type, n < 0, in_features < 1, layer_size
+ * outside 1..256, num_quantiles outside 1..64, num_actions outside 1..64, n_cos != 64, state_stride < in_features, num_envs < 1 or an
+ * agent key outside [0, SGW_MAX_AGENTS) (idx == NULL) or epoch >= 2^28 where taus are drawn, a misaligned pointer, a missing or short
+ * workspace, a non-zero reserved field, offsets beyond 64 bits -- is SGW_EINVAL with the reason in sgw_last_error(), before anything is
+ * launched.  n == 0 launches nothing and writes nothing. */
+#define SGW_STREAM_TAU 11u           /* (unsigned) index = (agent << 4) | (quantile >> 2), word quantile & 3, turn = the turn in flight: sgw_iqn_forward's taus */
+#define SGW_IQN_STATE_F32 0          /* state_type: the states are float32 */
+#define SGW_IQN_STATE_U8 1           /* ... uint8 (a TurnBuffer's) */
+#define SGW_IQN_MAX_LAYER 256
+#define SGW_IQN_MAX_ACTIONS 64       /* of sgw_iqn_forward (sgw_iqn_loss takes 256) */
+#define SGW_IQN_N_COS 64
+typedef struct sgw_iqn_forward_desc {
+    const void* states;          /* [n] rows of in_features elements of state_type, state_stride elements apart */
+    const float* w_head;         /* [L][D] */
+    const float* b_head;         /* [L] */
+    const float* w_cos;          /* [L][64] */
+    const float* b_cos;          /* [L] */
+    const float* w_ff;           /* [L][L] */
+    const float* b_ff;           /* [L] */
+    const float* w_adv;          /* [A][L] */
+    const float* b_adv;          /* [A] */
+    const float* w_val;          /* [L] */
+    const float* b_val;          /* [1] */
+    const float* taus;           /* [n][N], or NULL: drawn */
+    const int64_t* idx;          /* [n] row keys agent * num_envs + env of the drawn taus, or NULL */
+    float* out_qvalues;          /* [n][A], or NULL */
+    float* out_quantiles;        /* [n][N][A], or NULL */
+    float* out_taus;             /* [n][N], or NULL */
+    float* out_cos;              /* [n][N][64], or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t n, state_stride, num_envs;
+    uint64_t seed, first_env;    /* as in sgw_policy_desc */
+    uint32_t epoch, turn;
+    int32_t in_features, layer_size, num_quantiles, num_actions, n_cos, state_type, agent0;
+    int32_t reserved0, reserved1;    /* reserved: 0 */
+} sgw_iqn_forward_desc;
+int sgw_iqn_forward(const sgw_iqn_forward_desc* desc, void* stream);
+/* Bytes of workspace a call over n rows needs (0 for no rows); a negative code for n < 0 or layer_size outside 1..256. */
+int64_t sgw_iqn_forward_workspace_bytes(int64_t n, int32_t layer_size);
+/* The same two launches under the turn protocol (sgw_turn_*): seed and first_env come from the engine, num_envs = the engine's, agent0 =
+ * `agent`, idx must be NULL; epoch and the turn in flight (= completed + 1) are read from the device's turn state, as
+ * sgw_turn_policy_sample reads them (desc's seed, first_env, num_envs, agent0, epoch and turn are ignored).  Same arguments every turn:
+ * recordable. */
+int sgw_turn_iqn_forward(sgw_engine* eng, int32_t agent, const sgw_iqn_forward_desc* desc, void* stream);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

@@ -31,6 +31,7 @@ SAMPLE_F32, SAMPLE_U8 = 0, 1
 SAMPLE_ACT_I64, SAMPLE_ACT_U8 = 0, 1
 RETURNS_NORM_NONE, RETURNS_NORM_COLUMN, RETURNS_NORM_ALL = 0, 1, 2
 RETURNS_OUT_F64, RETURNS_OUT_F32 = 0, 1
+STREAM_TAU = 11             # sgw_iqn_forward's taus: index = (agent << 4) | (quantile >> 2), word quantile & 3, turn = the turn in flight
 STREAM_POLICY = 10          # sgw_policy_sample's draw: index = agent, turn = the turn in flight (STREAM_EXPLORE's layout)
 POLICY_F32, POLICY_F64 = 0, 1
 POLICY_PROBS, POLICY_LOGITS = 0, 1
@@ -212,6 +213,26 @@ class SgwIqnLossDesc(C.Structure):
     ]
 
 
+class SgwIqnForwardDesc(C.Structure):
+    """Mirror of ``struct sgw_iqn_forward_desc`` (include/sgw.h): one ``sgw_iqn_forward`` call; layout checked by tests/test_iqn_forward_cpu.py."""
+
+    _fields_ = [
+        ("states", C.c_void_p),
+        ("w_head", C.c_void_p), ("b_head", C.c_void_p), ("w_cos", C.c_void_p), ("b_cos", C.c_void_p), ("w_ff", C.c_void_p), ("b_ff", C.c_void_p),
+        ("w_adv", C.c_void_p), ("b_adv", C.c_void_p), ("w_val", C.c_void_p), ("b_val", C.c_void_p),
+        ("taus", C.c_void_p), ("idx", C.c_void_p),
+        ("out_qvalues", C.c_void_p), ("out_quantiles", C.c_void_p), ("out_taus", C.c_void_p), ("out_cos", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("n", C.c_int64), ("state_stride", C.c_int64), ("num_envs", C.c_int64),
+        ("seed", C.c_uint64), ("first_env", C.c_uint64),
+        ("epoch", C.c_uint32), ("turn", C.c_uint32),
+        ("in_features", C.c_int32), ("layer_size", C.c_int32), ("num_quantiles", C.c_int32), ("num_actions", C.c_int32), ("n_cos", C.c_int32),
+        ("state_type", C.c_int32), ("agent0", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 class SgwAdamTensor(C.Structure):
     """Mirror of ``struct sgw_adam_tensor`` (include/sgw.h): one tensor of an ``sgw_adam_plan`` call; layout checked by tests/test_adam_step_cpu.py."""
 
@@ -268,6 +289,7 @@ EXPORTS = (
     "sgw_ppo_loss", "sgw_ppo_loss_workspace_bytes",
     "sgw_iqn_loss", "sgw_iqn_loss_workspace_bytes",
     "sgw_adam_plan_bytes", "sgw_adam_plan", "sgw_adam_step",
+    "sgw_iqn_forward", "sgw_iqn_forward_workspace_bytes", "sgw_turn_iqn_forward",
     "sgw_last_error", "sgw_version",
 )
 
@@ -425,6 +447,12 @@ def load():
     lib.sgw_iqn_loss.restype = C.c_int
     lib.sgw_iqn_loss_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.sgw_iqn_loss_workspace_bytes.restype = C.c_int64
+    lib.sgw_iqn_forward.argtypes = [C.POINTER(SgwIqnForwardDesc), vp]
+    lib.sgw_iqn_forward.restype = C.c_int
+    lib.sgw_iqn_forward_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.sgw_iqn_forward_workspace_bytes.restype = C.c_int64
+    lib.sgw_turn_iqn_forward.argtypes = [vp, C.c_int32, C.POINTER(SgwIqnForwardDesc), vp]
+    lib.sgw_turn_iqn_forward.restype = C.c_int
     lib.sgw_adam_plan_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.sgw_adam_plan_bytes.restype = C.c_int64
     lib.sgw_adam_plan.argtypes = [C.POINTER(SgwAdamTensor), C.c_int64, C.c_int32, vp, C.c_int64, C.POINTER(SgwAdamPlanInfo)]

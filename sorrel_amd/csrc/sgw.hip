@@ -78,6 +78,7 @@ namespace {
 #include "ppo_loss.h"
 #include "iqn_loss.h"
 #include "adam_step.h"
+#include "iqn_forward.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -99,7 +100,7 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(SGW_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss, sgw_adam_step) ask of their arguments
+// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss, sgw_adam_step, sgw_iqn_forward) ask of their arguments
 inline uintptr_t at(const void* q) { return reinterpret_cast<uintptr_t>(q); }
 // is any of these pointers off the alignment `mask` + 1?  (NULL, an optional argument or one of another type, is aligned to everything)
 inline bool misaligned(const uintptr_t mask, std::initializer_list<const void*> ptrs) {
@@ -1534,6 +1535,83 @@ int sgw_iqn_loss(const sgw_iqn_loss_desc* d, void* stream) {
     HIP_TRY(hipGetLastError());
     LAUNCH_TRY(iqn_loss_merge_kernel, 1, s, p);
     return SGW_OK;
+}
+
+// ---------------------------------------------------------------- IQN's network forward (iqn_forward.h)
+int64_t sgw_iqn_forward_workspace_bytes(int64_t n, int32_t layer_size) {
+    if (n < 0 || n > INT64_MAX / 4096) return fail(SGW_EINVAL, "sgw_iqn_forward_workspace_bytes: n = %lld outside [0, 2^51)", (long long)n);
+    if (layer_size < 1 || layer_size > kFwdMaxL) return fail(SGW_EINVAL, "sgw_iqn_forward_workspace_bytes: layer_size = %d outside [1, %d]", layer_size, kFwdMaxL);
+    return n * layer_size * (int64_t)sizeof(float);
+}
+
+static int iqn_forward_launch(const sgw_iqn_forward_desc* d, const TurnState* ts, const char* who, void* stream) {
+    if (!d->states || !d->w_head || !d->b_head || !d->w_cos || !d->b_cos || !d->w_ff || !d->b_ff || !d->w_adv || !d->b_adv || !d->w_val || !d->b_val)
+        return fail(SGW_EINVAL, "%s: states and the ten weight pointers must not be NULL", who);
+    if (!d->out_qvalues && !d->out_quantiles) return fail(SGW_EINVAL, "%s: one of out_qvalues and out_quantiles must be given", who);
+    if (d->n < 0) return fail(SGW_EINVAL, "%s: n = %lld", who, (long long)d->n);
+    if (d->in_features < 1) return fail(SGW_EINVAL, "%s: in_features = %d", who, d->in_features);
+    if (d->layer_size < 1 || d->layer_size > kFwdMaxL) return fail(SGW_EINVAL, "%s: layer_size = %d outside [1, %d]", who, d->layer_size, kFwdMaxL);
+    if (d->num_quantiles < 1 || d->num_quantiles > kFwdM) return fail(SGW_EINVAL, "%s: num_quantiles = %d outside [1, %d]", who, d->num_quantiles, kFwdM);
+    if (d->num_actions < 1 || d->num_actions > SGW_IQN_MAX_ACTIONS) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, d->num_actions, SGW_IQN_MAX_ACTIONS);
+    if (d->n_cos != SGW_IQN_N_COS) return fail(SGW_EINVAL, "%s: n_cos = %d: only %d is built", who, d->n_cos, SGW_IQN_N_COS);
+    if (d->state_type != SGW_IQN_STATE_F32 && d->state_type != SGW_IQN_STATE_U8) return fail(SGW_EINVAL, "%s: unknown state_type %d", who, d->state_type);
+    if (d->state_stride < d->in_features) return fail(SGW_EINVAL, "%s: state_stride = %lld is smaller than in_features = %d", who, (long long)d->state_stride, d->in_features);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
+    if (!d->taus) {                           // the draw's key
+        if (d->num_envs < 1) return fail(SGW_EINVAL, "%s: num_envs = %lld", who, (long long)d->num_envs);
+        if (d->epoch >= (1u << 28)) return fail(SGW_EINVAL, "%s: epoch must be < 2^28", who);
+        if (!d->idx) {
+            const int64_t last = (int64_t)d->agent0 + (d->n > 0 ? (d->n - 1) / d->num_envs : 0);
+            if (d->agent0 < 0 || last >= SGW_MAX_AGENTS)
+                return fail(SGW_EINVAL, "%s: rows are keyed by agents %d .. %lld, outside [0, %d)", who, d->agent0, (long long)last, SGW_MAX_AGENTS);
+        }
+    }
+    if (d->state_type == SGW_IQN_STATE_F32 && misaligned(3, {d->states})) return fail(SGW_EINVAL, "%s: states is not aligned to its element type", who);
+    if (misaligned(3, {d->w_head, d->b_head, d->w_cos, d->b_cos, d->w_ff, d->b_ff, d->w_adv, d->b_adv, d->w_val, d->b_val, d->taus, d->out_qvalues,
+                       d->out_quantiles, d->out_taus, d->out_cos, d->workspace}))
+        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (a weight, taus, an output or the workspace)", who);
+    if (misaligned(7, {d->idx})) return fail(SGW_EINVAL, "%s: misaligned int64 pointer (idx)", who);
+    // the largest byte offsets: 4 n state_stride (states), 4 n N max(64, A) (out_cos, out_quantiles), 4 n L (the workspace)
+    if (d->n > INT64_MAX / 8 / d->state_stride || d->n > INT64_MAX / 8 / ((int64_t)kFwdM * kFwdMaxL))
+        return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->state_stride);
+    if (int rc = workspace_short(who, d->workspace, d->workspace_bytes, d->n * d->layer_size * (int64_t)sizeof(float))) return rc;
+    if (d->n == 0) return SGW_OK;
+    IqnFwdParams p{};
+    p.states = d->states;
+    p.w_head = d->w_head; p.b_head = d->b_head; p.w_cos = d->w_cos; p.b_cos = d->b_cos; p.w_ff = d->w_ff; p.b_ff = d->b_ff;
+    p.w_adv = d->w_adv; p.b_adv = d->b_adv; p.w_val = d->w_val; p.b_val = d->b_val; p.taus = d->taus; p.idx = d->idx;
+    p.out_q = d->out_qvalues; p.out_quant = d->out_quantiles; p.out_taus = d->out_taus; p.out_cos = d->out_cos;
+    p.h = static_cast<float*>(d->workspace);
+    p.ts = ts;
+    p.n = d->n; p.stride = d->state_stride; p.num_envs = d->taus ? 1 : d->num_envs;
+    p.D = d->in_features; p.L = d->layer_size; p.N = d->num_quantiles; p.A = d->num_actions; p.u8 = d->state_type == SGW_IQN_STATE_U8;
+    p.agent0 = d->agent0; p.R = kFwdM / d->num_quantiles;
+    p.head_tiles = ceil_div(d->n, kFwdM); p.q_tiles = ceil_div(d->n, p.R);
+    p.seed_lo = (uint32_t)d->seed; p.seed_hi = (uint32_t)(d->seed >> 32); p.first_env = (uint32_t)d->first_env;
+    p.epoch = d->epoch; p.turn = d->turn;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 head_grid((unsigned)std::min<int64_t>(p.head_tiles, kFwdMaxBlocks));
+    if (p.u8) hipLaunchKernelGGL(iqn_head_kernel<true>, head_grid, dim3(kFwdThreads), 0, s, p);
+    else hipLaunchKernelGGL(iqn_head_kernel<false>, head_grid, dim3(kFwdThreads), 0, s, p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(iqn_quantile_kernel, dim3((unsigned)std::min<int64_t>(p.q_tiles, kFwdMaxBlocks)), dim3(kFwdThreads), 0, s, p);
+    HIP_TRY(hipGetLastError());
+    return SGW_OK;
+}
+
+int sgw_iqn_forward(const sgw_iqn_forward_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_iqn_forward: desc is NULL");
+    return iqn_forward_launch(d, nullptr, "sgw_iqn_forward", stream);
+}
+
+int sgw_turn_iqn_forward(sgw_engine* e, int32_t agent, const sgw_iqn_forward_desc* desc, void* stream) {
+    if (!e) return fail(SGW_EINVAL, "sgw_turn_iqn_forward: NULL engine");
+    if (!desc) return fail(SGW_EINVAL, "sgw_turn_iqn_forward: desc is NULL");
+    if (agent < 0 || agent >= e->cfg.num_agents) return fail(SGW_EINVAL, "sgw_turn_iqn_forward: agent %d out of range", agent);
+    if (desc->idx) return fail(SGW_EINVAL, "sgw_turn_iqn_forward: idx must be NULL (the rows are the agent's envs in order)");
+    sgw_iqn_forward_desc d = *desc;
+    d.num_envs = e->cfg.num_envs; d.seed = e->cfg.seed; d.first_env = e->cfg.first_env_id; d.agent0 = agent; d.epoch = 0; d.turn = 0;
+    return iqn_forward_launch(&d, e->d_turn, "sgw_turn_iqn_forward", stream);
 }
 
 // ---------------------------------------------------------------- Adam, clipping and the soft update (adam_step.h)

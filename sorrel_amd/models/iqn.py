@@ -1,0 +1,310 @@
+"""IQN's Q-network (``sorrel/models/pytorch/iqn.py:51-167`` and ``layers.py``'s ``NoisyLinear``): the modules, with the reference's
+parameter and buffer names and shapes so that its ``state_dict`` loads, and the forward pass on the device.
+
+* ``IQN.forward(input, n_tau)`` is the reference's sequence of torch ops: it supports autograd, runs on the CPU and is the baseline.
+* ``IQN.quantiles`` / ``IQN.get_qvalues`` run ``sgw_iqn_forward`` (``sorrel_amd/csrc/iqn_forward.h``: two launches, nothing of size
+  ``[B N, L]`` through memory) for device tensors, without autograd: acting, and the two ``next_states`` calls of a learner's step.  The
+  taus are given, or drawn KEYED by (seed, env, epoch, turn, agent, quantile) so that a recorded turn draws fresh ones on every replay.
+* ``IQNActor`` is a ``BaseModel`` around an ``IQN`` whose ``take_action`` returns the float32 ``[E, A]`` action values: the act launch takes
+  the argmax and explores (``SGW_ACT_QF32``).  It has no ``train_step``, no optimiser and no target network.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from sorrel_amd.models.base_model import BaseModel
+
+N_COS = 64
+MAX_LAYER, MAX_QUANTILES, MAX_ACTIONS = 256, 64, 64
+
+
+class NoisyLinear(nn.Linear):
+    """``layers.py:9-65``: a linear layer whose training-mode weights are ``weight + sigma_weight * epsilon_weight`` with fresh normal
+    ``epsilon`` per call; in eval mode the mean weights."""
+
+    def __init__(self, in_features: int, out_features: int, sigma_init: float = 0.017, bias: bool = True) -> None:
+        super().__init__(in_features, out_features, bias=bias)
+        self.sigma_weight = nn.Parameter(torch.full((out_features, in_features), sigma_init))
+        self.register_buffer("epsilon_weight", torch.zeros(out_features, in_features))
+        if bias:
+            self.sigma_bias = nn.Parameter(torch.full((out_features,), sigma_init))
+            self.register_buffer("epsilon_bias", torch.zeros(out_features))
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        std = math.sqrt(3 / self.in_features)
+        self.weight.data.uniform_(-std, std)
+        self.bias.data.uniform_(-std, std)
+
+    def effective(self, resample: bool = True):
+        """The (weight, bias) this layer applies now: in training mode new noise is drawn first (``resample``), as ``forward`` does."""
+        if not self.training:
+            return self.weight, self.bias
+        if resample:
+            self.epsilon_weight.normal_()
+        weight = self.weight + self.sigma_weight * self.epsilon_weight
+        bias = None
+        if self.bias is not None:
+            if resample:
+                self.epsilon_bias.normal_()
+            bias = self.bias + self.sigma_bias * self.epsilon_bias
+        return weight, bias
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        weight, bias = self.effective()
+        return F.linear(input, weight, bias)
+
+
+class IQNOutput:
+    """What ``IQN.quantiles`` gives back: ``quantiles`` float32 ``[B, N, A]``, ``taus`` ``[B, N, 1]``, ``qvalues`` ``[B, A]`` (the mean over
+    the quantiles) and, if asked for, ``cos`` ``[B, N, 64]``, else None.  Passed back as ``out=`` its tensors are overwritten in place."""
+
+    __slots__ = ("quantiles", "taus", "qvalues", "cos", "_workspace", "_weights")
+
+    def __init__(self, B: int, N: int, A: int, L: int, device, cos: bool = False):
+        self.quantiles = torch.empty((B, N, A), dtype=torch.float32, device=device)
+        self.taus = torch.empty((B, N, 1), dtype=torch.float32, device=device)
+        self.qvalues = torch.empty((B, A), dtype=torch.float32, device=device)
+        self.cos = torch.empty((B, N, N_COS), dtype=torch.float32, device=device) if cos else None
+        self._workspace = torch.empty((max(B * L, 1),), dtype=torch.float32, device=device)
+        self._weights = None                  # training mode: where the effective noisy weights are composed (fixed addresses)
+
+    def __repr__(self):
+        return f"IQNOutput(n={self.quantiles.shape[0]}, num_quantiles={self.quantiles.shape[1]}, num_actions={self.quantiles.shape[2]})"
+
+
+class IQN(nn.Module):
+    """The IQN Q-network (``iqn.py:51-167``)."""
+
+    def __init__(self, input_size: Sequence[int], action_space: int, layer_size: int, seed: int, n_quantiles: int, n_frames: int = 5,
+                 device="cpu") -> None:
+        super().__init__()
+        self.seed = torch.manual_seed(seed)
+        self.key_seed = int(seed)
+        self.input_shape = np.array(input_size)
+        self.state_dim = len(self.input_shape)
+        self.action_space = action_space
+        self.n_quantiles = n_quantiles
+        self.n_cos = N_COS
+        self.layer_size = layer_size
+        self.pis = torch.FloatTensor([np.pi * i for i in range(1, self.n_cos + 1)]).view(1, 1, self.n_cos).to(device)
+        self.device = device
+        self.head1 = nn.Linear(int(n_frames * self.input_shape.prod()), layer_size)
+        self.cos_embedding = nn.Linear(self.n_cos, layer_size)
+        self.ff_1 = NoisyLinear(layer_size, layer_size)
+        self.cos_layer_out = layer_size
+        self.advantage = NoisyLinear(layer_size, action_space)
+        self.value = NoisyLinear(layer_size, 1)
+        self._calls = 0                       # the turn of an unkeyed device call's draws: every call draws other taus
+        self.to(device)
+
+    # ------------------------------------------------------------------------------------------------ the torch-op path (the baseline)
+    def calc_cos(self, batch_size: int, n_tau: int = 8):
+        taus = torch.rand(batch_size, n_tau).unsqueeze(-1).to(self.pis.device)
+        cos = torch.cos(taus * self.pis)
+        assert cos.shape == (batch_size, n_tau, self.n_cos), "cos shape is incorrect"
+        return cos, taus
+
+    def forward(self, input: torch.Tensor, n_tau: int = 8):
+        batch_size = input.size()[0]
+        r_in = input.view(batch_size, -1)
+        x = torch.relu(self.head1(r_in))
+        cos, taus = self.calc_cos(batch_size, n_tau)
+        cos = cos.view(batch_size * n_tau, self.n_cos)
+        cos = torch.relu(self.cos_embedding(cos))
+        cos_x = cos.view(batch_size, n_tau, self.cos_layer_out)
+        x = (x.unsqueeze(1) * cos_x).view(batch_size * n_tau, self.cos_layer_out)
+        x = torch.relu(self.ff_1(x))
+        advantage = self.advantage(x)
+        value = self.value(x)
+        out = value + advantage - advantage.mean(dim=1, keepdim=True)
+        return out.view(batch_size, n_tau, self.action_space), taus
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        self.pis = fn(self.pis)
+        return self
+
+    # ------------------------------------------------------------------------------------------------ the device path
+    def effective_weights(self, out: Optional[IQNOutput] = None, resample: bool = True):
+        """The ten tensors ``sgw_iqn_forward`` takes, detached: in eval mode the parameters themselves; in training mode
+        ``weight + sigma * epsilon`` of the three noisy layers with fresh noise (``resample``), composed into ``out``'s storage if given."""
+        with torch.no_grad():
+            ws = [self.head1.weight, self.head1.bias, self.cos_embedding.weight, self.cos_embedding.bias]
+            noisy = [self.ff_1.effective(resample), self.advantage.effective(resample), self.value.effective(resample)]
+            if self.training and out is not None:
+                if out._weights is None:
+                    out._weights = [torch.empty_like(t) for pair in noisy for t in pair]
+                for dst, src in zip(out._weights, [t for pair in noisy for t in pair]):
+                    dst.copy_(src)
+                ws += out._weights
+            else:
+                ws += [t for pair in noisy for t in pair]
+            return [w.detach() for w in ws]
+
+    def _check_states(self, states):
+        if not torch.is_tensor(states):
+            raise TypeError(f"states must be a tensor, not {type(states).__name__}")
+        if states.dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"states must be float32 or uint8, not {states.dtype}")
+        if states.dim() < 1:
+            raise ValueError("states must be [B, ...]")
+        B = int(states.shape[0])
+        flat = states.reshape(B, -1)
+        D = self.head1.in_features
+        if flat.shape[1] != D:
+            raise ValueError(f"states hold {flat.shape[1]} elements per row; the head layer takes {D}")
+        if flat.stride(1) != 1 and B > 0 and D > 1:
+            raise ValueError("the elements of a state row must be contiguous")
+        return B, flat
+
+    def quantiles(self, states, n_tau: Optional[int] = None, *, taus=None, key=None, out: Optional[IQNOutput] = None, cos: bool = False,
+                  engine=None, agent: Optional[int] = None):
+        """The quantiles of ``states`` (float32 or uint8 ``[B, ...]``), without autograd: an ``IQNOutput``.  ``taus`` (float32 ``[B, N]`` or
+        ``[B, N, 1]``) are used as given; otherwise they are drawn keyed: ``key`` is a dict of ``seed``, ``epoch``, ``turn``, ``num_envs``,
+        ``agent0``, ``first_env`` and ``idx`` (all optional; without a key every call of this module draws other taus), or
+        ``engine=, agent=`` runs ``sgw_turn_iqn_forward``, which reads epoch and turn from the engine's turn state (recordable).  Honours
+        ``training``: the noisy layers' effective weights are composed first.  On a HIP device this is one ``sgw_iqn_forward`` call; with
+        ``out=`` (an earlier result for the same shapes) it allocates nothing and does not synchronise.  CPU tensors run the torch ops."""
+        B, flat = self._check_states(states)
+        N = int(self.n_quantiles if n_tau is None else n_tau)
+        A, L = int(self.action_space), int(self.layer_size)
+        if not 1 <= N <= MAX_QUANTILES:
+            raise ValueError(f"{N} quantiles: the forward takes 1..{MAX_QUANTILES}")
+        if not 1 <= A <= MAX_ACTIONS:
+            raise ValueError(f"{A} actions: the forward takes 1..{MAX_ACTIONS}")
+        if not 1 <= L <= MAX_LAYER:
+            raise ValueError(f"layer_size = {L}: the forward takes 1..{MAX_LAYER}")
+        dev = flat.device
+        if self.head1.weight.device != dev:
+            raise ValueError(f"states are on {dev}, the network on {self.head1.weight.device}")
+        if taus is not None:
+            if not torch.is_tensor(taus) or taus.dtype != torch.float32:
+                raise TypeError("taus must be a float32 tensor")
+            if tuple(taus.shape) not in ((B, N), (B, N, 1)) or not taus.is_contiguous() or taus.device != dev:
+                raise ValueError(f"taus must be contiguous [{B}, {N}] or [{B}, {N}, 1] on {dev}; got {tuple(taus.shape)} on {taus.device}")
+        if out is None:
+            res = IQNOutput(B, N, A, L, dev, cos)
+        else:
+            if not isinstance(out, IQNOutput):
+                raise TypeError("out= takes an earlier IQNOutput")
+            if tuple(out.quantiles.shape) != (B, N, A) or out.quantiles.device != dev or out._workspace.numel() < B * L or (cos and out.cos is None):
+                raise ValueError("out= was made for other shapes or another device, or without the optional outputs asked for")
+            res = out
+        if dev.type != "cuda":
+            return self._quantiles_by_torch(flat, N, taus, res)
+        ws = self.effective_weights(res if out is not None else None)
+        for w in ws:
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                raise TypeError("the network's parameters must be contiguous float32")
+        if B == 0:
+            return res
+        from sorrel_amd import _native as N_
+
+        d = N_.SgwIqnForwardDesc()
+        d.states = flat.data_ptr()
+        (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
+        d.out_qvalues, d.out_quantiles, d.out_taus = res.qvalues.data_ptr(), res.quantiles.data_ptr(), res.taus.data_ptr()
+        if res.cos is not None and cos:
+            d.out_cos = res.cos.data_ptr()
+        d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 4
+        d.n, d.state_stride = B, int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), flat.shape[1])
+        d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = flat.shape[1], L, N, A, N_COS
+        d.state_type = 1 if flat.dtype == torch.uint8 else 0
+        keep = None
+        if taus is not None:
+            d.taus = taus.data_ptr()
+        elif engine is None:
+            key = dict(key or {})
+            if not key:
+                self._calls += 1
+            d.seed = int(key.get("seed", self.key_seed)) & 0xFFFFFFFFFFFFFFFF
+            d.epoch, d.turn = int(key.get("epoch", 0)), int(key.get("turn", self._calls)) & 0xFFFFFFFF
+            d.num_envs, d.agent0, d.first_env = int(key.get("num_envs", max(B, 1))), int(key.get("agent0", 0)), int(key.get("first_env", 0))
+            keep = key.get("idx")
+            if keep is not None:
+                if keep.dtype != torch.int64 or tuple(keep.shape) != (B,) or not keep.is_contiguous() or keep.device != dev:
+                    raise ValueError(f"key['idx'] must be contiguous int64 [{B}] on {dev}")
+                d.idx = keep.data_ptr()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            if engine is not None and taus is None:
+                if B != engine.num_envs:
+                    raise ValueError(f"the turn protocol's rows are the engine's {engine.num_envs} envs; got {B}")
+                N_.check(N_.load().sgw_turn_iqn_forward(engine._h, int(agent or 0), C.byref(d), stream))
+            else:
+                N_.check(N_.load().sgw_iqn_forward(C.byref(d), stream))
+        return res
+
+    def _quantiles_by_torch(self, flat, N, taus, res):
+        with torch.no_grad():
+            B = flat.shape[0]
+            x = torch.relu(self.head1(flat.float()))
+            t = (torch.rand(B, N, device=flat.device) if taus is None else taus).reshape(B, N, 1)
+            c = torch.cos(t * self.pis)
+            e = torch.relu(self.cos_embedding(c.view(B * N, self.n_cos))).view(B, N, self.layer_size)
+            z = (x.unsqueeze(1) * e).view(B * N, self.layer_size)
+            y = torch.relu(self.ff_1(z))
+            adv, val = self.advantage(y), self.value(y)
+            q = (val + adv - adv.mean(dim=1, keepdim=True)).view(B, N, self.action_space)
+            res.quantiles.copy_(q)
+            res.taus.copy_(t)
+            res.qvalues.copy_(q.mean(dim=1))
+            if res.cos is not None:
+                res.cos.copy_(c)
+        return res
+
+    def get_qvalues(self, inputs, n_tau: Optional[int] = None, **kwargs):
+        """The mean of the quantiles, float32 ``[B, A]`` (``iqn.py:164-167``).  Tensors that require no kernel -- the CPU, or a call under
+        autograd with ``requires_grad`` inputs -- take ``forward``; device tensors take ``quantiles`` (same keywords) and come detached."""
+        if inputs.device.type != "cuda":
+            if kwargs.get("taus") is None and kwargs.get("out") is None:
+                quantiles, _ = self.forward(inputs, self.n_quantiles if n_tau is None else n_tau)
+                return quantiles.mean(dim=1)
+        return self.quantiles(inputs, n_tau, **kwargs).qvalues
+
+
+class IQNActor(BaseModel):
+    """A policy that acts through an ``IQN``: ``take_action(state)`` returns the float32 ``[E, A]`` action values, so the act launch takes the
+    argmax and explores with ``epsilon`` (``SGW_ACT_QF32``).  ``bind(env, slot)`` tells it whose turn its taus are keyed by: eagerly the
+    environment's (seed, epoch, turn) go into the call; under ``capture_turn()`` it uses ``sgw_turn_iqn_forward``, which reads them on the
+    device, so a replayed turn draws new taus.  No ``train_step``, no optimiser, no target network."""
+
+    def __init__(self, input_size, action_space: int, layer_size: int = 250, n_quantiles: int = 12, n_frames: int = 1, seed: int = 0,
+                 memory_size: int = 0, epsilon: float = 0.0, num_envs: int = 1, device=None):
+        super().__init__(input_size, action_space, memory_size=memory_size, epsilon=epsilon, num_envs=num_envs, device=device)
+        shape = tuple(input_size) if isinstance(input_size, Sequence) else (input_size,)
+        self.net = IQN(shape, action_space, layer_size, seed, n_quantiles, n_frames=n_frames, device=device or "cpu")
+        self.net.eval()
+        self._env = None
+        self._slot = 0
+        self._out = None
+
+    def bind(self, env, slot: int) -> "IQNActor":
+        self._env, self._slot = env, int(slot)
+        return self
+
+    def take_action(self, state):
+        B = int(state.shape[0])
+        if state.device.type != "cuda":
+            return self.net.get_qvalues(state.reshape(B, -1).float()).detach()
+        if self._out is None or self._out.quantiles.shape[0] != B or self._out.quantiles.device != state.device:
+            self._out = IQNOutput(B, self.net.n_quantiles, self.net.action_space, self.net.layer_size, state.device)
+        env = self._env
+        if env is None:
+            return self.net.quantiles(state, out=self._out).qvalues
+        eng = env._ensure_engine()
+        if getattr(env, "_mixed", False):
+            eng = env._agent_engine[self._slot]
+        if env._turn_capture:
+            return self.net.quantiles(state, out=self._out, engine=eng, agent=self._slot).qvalues
+        key = {"seed": int(eng.spec.seed), "epoch": int(env.epoch), "turn": int(env.turn), "num_envs": int(eng.num_envs), "agent0": self._slot,
+               "first_env": int(eng.first_env_id)}
+        return self.net.quantiles(state, out=self._out, key=key).qvalues
