@@ -38,6 +38,8 @@ POLICY_PROBS, POLICY_LOGITS = 0, 1
 POLICY_MAX_ACTIONS = 256
 PPO_ACT_I64, PPO_ACT_U8 = 0, 1
 IQN_MAX_QUANTILES = 64
+IQN_STATE_F32, IQN_STATE_U8 = 0, 1
+IQN_MAX_LAYER, IQN_MAX_ACTIONS, IQN_N_COS = 256, 64, 64      # of sgw_iqn_forward (sgw_iqn_loss takes POLICY_MAX_ACTIONS)
 ADAM_CLIP_NONE, ADAM_CLIP_NORM, ADAM_CLIP_COEF = 0, 1, 2
 ADAM_ZERO_GRADS = 1
 ADAM_MAX_TENSORS, ADAM_CHUNK = 4096, 4096
@@ -45,7 +47,7 @@ POLICY_INVALID_ACTION = 255  # the action of a row torch's Categorical would rai
 
 
 class SgwConfig(C.Structure):
-    """Mirror of ``struct sgw_config`` (include/sgw.h); layout checked by tests/test_abi.py."""
+    """Mirror of ``struct sgw_config`` (include/sgw.h); tests/test_abi.py checks the layout of every mirror in this module."""
 
     _fields_ = [
         ("height", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32),
@@ -168,7 +170,7 @@ class SgwReturnsDesc(C.Structure):
 
 
 class SgwPolicyDesc(C.Structure):
-    """Mirror of ``struct sgw_policy_desc`` (include/sgw.h): one ``sgw_policy_sample`` call; layout checked by tests/test_policy_cpu.py."""
+    """Mirror of ``struct sgw_policy_desc`` (include/sgw.h): one ``sgw_policy_sample`` call."""
 
     _fields_ = [
         ("dist", C.c_void_p), ("idx", C.c_void_p), ("out_actions", C.c_void_p), ("out_log_probs", C.c_void_p), ("out_entropy", C.c_void_p),
@@ -181,7 +183,7 @@ class SgwPolicyDesc(C.Structure):
 
 
 class SgwPpoLossDesc(C.Structure):
-    """Mirror of ``struct sgw_ppo_loss_desc`` (include/sgw.h): one ``sgw_ppo_loss`` call; layout checked by tests/test_ppo_loss_cpu.py."""
+    """Mirror of ``struct sgw_ppo_loss_desc`` (include/sgw.h): one ``sgw_ppo_loss`` call."""
 
     _fields_ = [
         ("dist", C.c_void_p), ("values", C.c_void_p), ("actions", C.c_void_p), ("old_log_probs", C.c_void_p), ("returns", C.c_void_p),
@@ -197,7 +199,7 @@ class SgwPpoLossDesc(C.Structure):
 
 
 class SgwIqnLossDesc(C.Structure):
-    """Mirror of ``struct sgw_iqn_loss_desc`` (include/sgw.h): one ``sgw_iqn_loss`` call; layout checked by tests/test_iqn_loss_cpu.py."""
+    """Mirror of ``struct sgw_iqn_loss_desc`` (include/sgw.h): one ``sgw_iqn_loss`` call."""
 
     _fields_ = [
         ("q_next_local", C.c_void_p), ("q_next_target", C.c_void_p), ("q_expected", C.c_void_p), ("taus", C.c_void_p),
@@ -214,7 +216,7 @@ class SgwIqnLossDesc(C.Structure):
 
 
 class SgwIqnForwardDesc(C.Structure):
-    """Mirror of ``struct sgw_iqn_forward_desc`` (include/sgw.h): one ``sgw_iqn_forward`` call; layout checked by tests/test_iqn_forward_cpu.py."""
+    """Mirror of ``struct sgw_iqn_forward_desc`` (include/sgw.h): one ``sgw_iqn_forward`` call."""
 
     _fields_ = [
         ("states", C.c_void_p),
@@ -234,7 +236,7 @@ class SgwIqnForwardDesc(C.Structure):
 
 
 class SgwAdamTensor(C.Structure):
-    """Mirror of ``struct sgw_adam_tensor`` (include/sgw.h): one tensor of an ``sgw_adam_plan`` call; layout checked by tests/test_adam_step_cpu.py."""
+    """Mirror of ``struct sgw_adam_tensor`` (include/sgw.h): one tensor of an ``sgw_adam_plan`` call."""
 
     _fields_ = [
         ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("target", C.c_void_p),
@@ -276,24 +278,83 @@ class SgwAdamStepDesc(C.Structure):
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
-# every symbol include/sgw.h declares
-EXPORTS = (
-    "sgw_create", "sgw_destroy", "sgw_reset", "sgw_observe", "sgw_step", "sgw_rollout", "sgw_reduce_metrics",
-    "sgw_random_actions", "sgw_set_obs_format", "sgw_bind_agent_state", "sgw_init_agent_state", "sgw_bind_agent_dir", "sgw_bind_target_types", "sgw_bind_encounters", "sgw_get_status", "sgw_obs_elems_per_env", "sgw_grid_bytes_per_env",
-    "sgw_algorithmic_bytes_per_env_step", "sgw_set_timing", "sgw_get_step_time_ms", "sgw_get_step_times_ms",
-    "sgw_set_auto_reset", "sgw_set_wg_per_cu", "sgw_launch_info", "sgw_capabilities", "sgw_observe_rows", "sgw_act", "sgw_observe_full",
-    "sgw_set_option", "sgw_plan", "sgw_jit_stats", "sgw_jit_compile", "sgw_bind_row_tail",
-    "sgw_turn_bind", "sgw_turn_set", "sgw_turn_begin", "sgw_turn_act", "sgw_turn_end", "sgw_turn_state", "sgw_turn_begin_rows", "sgw_turn_act_rows", "sgw_turn_epsilon", "sgw_turn_prev_rows", "sgw_turn_resolve", "sgw_gather_rows", "sgw_sweep_observe_rows", "sgw_choose_actions", "sgw_verify_rows", "sgw_apply_actions", "sgw_render", "sgw_sample",
-    "sgw_returns", "sgw_returns_workspace_bytes",
-    "sgw_policy_sample", "sgw_turn_policy_sample",
-    "sgw_ppo_loss", "sgw_ppo_loss_workspace_bytes",
-    "sgw_iqn_loss", "sgw_iqn_loss_workspace_bytes",
-    "sgw_adam_plan_bytes", "sgw_adam_plan", "sgw_adam_step",
-    "sgw_iqn_forward", "sgw_iqn_forward_workspace_bytes", "sgw_turn_iqn_forward",
-    "sgw_last_error", "sgw_version",
-)
+_rc, _vp, _i32, _u32, _i64, _f64 = C.c_int, C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_double    # (every data pointer is a void *)
+_vpp, _cfgp = C.POINTER(C.c_void_p), C.POINTER(SgwConfig)
+
+# every symbol include/sgw.h declares: name -> (restype, argtypes); tests/test_abi.py compares each with the header's declaration
+PROTOTYPES = {
+    "sgw_create": (_rc, [_cfgp, C.POINTER(_vp)]),
+    "sgw_destroy": (None, [_vp]),
+    "sgw_reset": (_rc, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    "sgw_observe": (_rc, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "sgw_step": (_rc, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _i32, _i32, _u32, _vp]),
+    "sgw_rollout": (_rc, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _i64, _i64, _i64, _u32, _vp]),
+    "sgw_reduce_metrics": (_rc, [_vp, _vp, _vp, _vp]),
+    "sgw_random_actions": (_rc, [_vp, _vp, _u32, _u32, _vp]),
+    "sgw_set_obs_format": (_rc, [_vp, C.c_int]),
+    "sgw_bind_agent_state": (_rc, [_vp, _vp, _vp]),
+    "sgw_bind_agent_dir": (_rc, [_vp, _vp]),
+    "sgw_bind_target_types": (_rc, [_vp, _vp]),
+    "sgw_bind_encounters": (_rc, [_vp, _vp, _vp, _i32]),
+    "sgw_init_agent_state": (_rc, [_vp, _vp, _vp]),
+    "sgw_get_status": (_rc, [_vp, C.POINTER(_i32), _vp]),
+    "sgw_obs_elems_per_env": (_i64, [_cfgp]),
+    "sgw_grid_bytes_per_env": (_i64, [_cfgp]),
+    "sgw_algorithmic_bytes_per_env_step": (_i64, [_cfgp]),
+    "sgw_set_timing": (_rc, [_vp, C.c_int]),
+    "sgw_get_step_time_ms": (_rc, [_vp, C.POINTER(_f64), C.POINTER(_i64)]),
+    "sgw_get_step_times_ms": (_rc, [_vp, C.POINTER(C.c_float), _i64, C.POINTER(_i64)]),
+    "sgw_set_auto_reset": (_rc, [_vp, _u32, _vp]),
+    "sgw_set_wg_per_cu": (_rc, [_vp, C.c_int]),
+    "sgw_launch_info": (_rc, [_vp, C.c_char_p, _i64]),
+    "sgw_observe_full": (_rc, [_vp, _vp, _vp, _vp]),
+    "sgw_capabilities": (_rc, [_vp]),
+    "sgw_observe_rows": (_rc, [_vp, _vp, _vp, _vpp, _i64, _i32, _i32, _vp]),
+    "sgw_sweep_observe_rows": (_rc, [_vp, _vp, _vp, _vpp, _i64, _u32, _u32, _u32, _vp]),
+    "sgw_act": (_rc, [_vp, _vp, _vp, _vp, _vpp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "sgw_set_option": (_rc, [_vp, C.c_char_p, C.c_char_p]),
+    "sgw_plan": (_rc, [_cfgp, _i32, _i64, C.POINTER(SgwPlan)]),
+    "sgw_jit_compile": (_rc, [C.c_char_p, C.c_char_p, C.c_char_p, _i64]),
+    "sgw_jit_stats": (_rc, [C.POINTER(_f64)]),
+    "sgw_bind_row_tail": (_rc, [_vp, C.c_int, C.c_int, _vp]),
+    "sgw_turn_bind": (_rc, [_vp, C.POINTER(SgwTurnRows)]),
+    "sgw_turn_set": (_rc, [_vp, _u32, _u32, _vp]),
+    "sgw_turn_begin": (_rc, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "sgw_turn_act": (_rc, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "sgw_turn_begin_rows": (_rc, [_vp, _vp, _vp, _vp, _vp, _vp, _vpp, _i64, _u32, _vp]),
+    "sgw_turn_act_rows": (_rc, [_vp, _vp, _vp, _vp, _vpp, _i64, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "sgw_turn_end": (_rc, [_vp, _vp, _vp]),
+    "sgw_turn_state": (_rc, [_vp, C.POINTER(_u32), C.POINTER(_i64), _vp]),
+    "sgw_turn_resolve": (_rc, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "sgw_gather_rows": (_rc, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "sgw_verify_rows": (_rc, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "sgw_apply_actions": (_rc, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "sgw_choose_actions": (_rc, [_vp, _vp, _vp, _i64, _u32, _u32, _vp, _vp]),
+    "sgw_turn_prev_rows": (_rc, [_vp, _i32, _i32, _vp, _vp]),
+    "sgw_turn_epsilon": (_rc, [_vp, _i32, _f64, _vp]),
+    "sgw_render": (_rc, [C.POINTER(SgwRenderDesc), _vp]),
+    "sgw_sample": (_rc, [C.POINTER(SgwSampleDesc), _vp]),
+    "sgw_returns": (_rc, [C.POINTER(SgwReturnsDesc), _vp]),
+    "sgw_returns_workspace_bytes": (_i64, [_i64, _i64]),
+    "sgw_policy_sample": (_rc, [C.POINTER(SgwPolicyDesc), _vp]),
+    "sgw_turn_policy_sample": (_rc, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "sgw_ppo_loss": (_rc, [C.POINTER(SgwPpoLossDesc), _vp]),
+    "sgw_ppo_loss_workspace_bytes": (_i64, [_i64]),
+    "sgw_iqn_loss": (_rc, [C.POINTER(SgwIqnLossDesc), _vp]),
+    "sgw_iqn_loss_workspace_bytes": (_i64, [_i64, _i32]),
+    "sgw_iqn_forward": (_rc, [C.POINTER(SgwIqnForwardDesc), _vp]),
+    "sgw_iqn_forward_workspace_bytes": (_i64, [_i64, _i32]),
+    "sgw_turn_iqn_forward": (_rc, [_vp, _i32, C.POINTER(SgwIqnForwardDesc), _vp]),
+    "sgw_adam_plan_bytes": (_i64, [_i64, _i64]),
+    "sgw_adam_plan": (_rc, [C.POINTER(SgwAdamTensor), _i64, _i32, _vp, _i64, C.POINTER(SgwAdamPlanInfo)]),
+    "sgw_adam_step": (_rc, [C.POINTER(SgwAdamStepDesc), _vp]),
+    "sgw_last_error": (C.c_char_p, []),
+    "sgw_version": (C.c_char_p, []),
+}
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
+_torch = None        # torch, kept by load() (imported there, not here: importing this module stays free of it)
 
 
 class SgwError(RuntimeError):
@@ -314,7 +375,7 @@ def _hip_runtimes_mapped():
 
 def load():
     """Load libsgw.so (after torch, so that it binds to torch's HIP runtime)."""
-    global _lib
+    global _lib, _torch
     if _lib is not None:
         return _lib
     if not os.path.isfile(LIB_PATH):
@@ -322,148 +383,16 @@ def load():
             f"HIP extension not built: {LIB_PATH} is missing. Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the step/observe path."
         )
-    import torch  # noqa: F401  (maps torch's libamdhip64 first; libsgw.so then resolves to the same soname)
+    import torch  # (maps torch's libamdhip64 first; libsgw.so then resolves to the same soname)
 
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     rts = _hip_runtimes_mapped()
     if len(rts) > 1:
         raise SgwError(f"two HIP runtimes are mapped in this process ({rts}); stream handles would not be shared")
-    vp, u8p, f32p, f64p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
-    cfgp = C.POINTER(SgwConfig)
-    lib.sgw_create.argtypes = [cfgp, C.POINTER(vp)]
-    lib.sgw_create.restype = C.c_int
-    lib.sgw_destroy.argtypes = [vp]
-    lib.sgw_destroy.restype = None
-    lib.sgw_reset.argtypes = [vp, u8p, u8p, f64p, C.c_uint32, vp]
-    lib.sgw_reset.restype = C.c_int
-    lib.sgw_observe.argtypes = [vp, u8p, u8p, f32p, C.c_int32, C.c_int32, vp]
-    lib.sgw_observe.restype = C.c_int
-    lib.sgw_step.argtypes = [vp, u8p, u8p, u8p, f32p, f32p, f64p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
-                             C.c_uint32, vp]
-    lib.sgw_step.restype = C.c_int
-    lib.sgw_rollout.argtypes = [vp, u8p, u8p, u8p, f32p, f32p, f64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64,
-                                C.c_int64, C.c_uint32, vp]
-    lib.sgw_rollout.restype = C.c_int
-    lib.sgw_reduce_metrics.argtypes = [vp, f64p, f64p, vp]
-    lib.sgw_reduce_metrics.restype = C.c_int
-    lib.sgw_random_actions.argtypes = [vp, u8p, C.c_uint32, C.c_uint32, vp]
-    lib.sgw_random_actions.restype = C.c_int
-    lib.sgw_set_obs_format.argtypes = [vp, C.c_int]
-    lib.sgw_set_obs_format.restype = C.c_int
-    lib.sgw_bind_agent_state.argtypes = [vp, u8p, u8p]
-    lib.sgw_bind_agent_state.restype = C.c_int
-    lib.sgw_bind_agent_dir.argtypes = [vp, u8p]
-    lib.sgw_bind_agent_dir.restype = C.c_int
-    lib.sgw_bind_target_types.argtypes = [vp, u8p]
-    lib.sgw_bind_target_types.restype = C.c_int
-    lib.sgw_bind_encounters.argtypes = [vp, vp, vp, C.c_int32]
-    lib.sgw_bind_encounters.restype = C.c_int
-    lib.sgw_init_agent_state.argtypes = [vp, u8p, vp]
-    lib.sgw_init_agent_state.restype = C.c_int
-    lib.sgw_get_status.argtypes = [vp, C.POINTER(C.c_int32), vp]
-    lib.sgw_get_status.restype = C.c_int
-    for name in ("sgw_obs_elems_per_env", "sgw_grid_bytes_per_env", "sgw_algorithmic_bytes_per_env_step"):
-        getattr(lib, name).argtypes = [cfgp]
-        getattr(lib, name).restype = C.c_int64
-    lib.sgw_set_timing.argtypes = [vp, C.c_int]
-    lib.sgw_set_timing.restype = C.c_int
-    lib.sgw_get_step_time_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.sgw_get_step_time_ms.restype = C.c_int
-    lib.sgw_get_step_times_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]
-    lib.sgw_get_step_times_ms.restype = C.c_int
-    lib.sgw_set_auto_reset.argtypes = [vp, C.c_uint32, f64p]
-    lib.sgw_set_auto_reset.restype = C.c_int
-    lib.sgw_set_wg_per_cu.argtypes = [vp, C.c_int]
-    lib.sgw_set_wg_per_cu.restype = C.c_int
-    lib.sgw_launch_info.argtypes = [vp, C.c_char_p, C.c_int64]
-    lib.sgw_launch_info.restype = C.c_int
-    lib.sgw_observe_full.argtypes = [vp, u8p, vp, vp]
-    lib.sgw_observe_full.restype = C.c_int
-    lib.sgw_capabilities.argtypes = [vp]
-    lib.sgw_capabilities.restype = C.c_int
-    lib.sgw_observe_rows.argtypes = [vp, u8p, u8p, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_int32, vp]
-    lib.sgw_observe_rows.restype = C.c_int
-    lib.sgw_sweep_observe_rows.argtypes = [vp, u8p, u8p, C.POINTER(C.c_void_p), C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
-    lib.sgw_sweep_observe_rows.restype = C.c_int
-    lib.sgw_act.argtypes = [vp, u8p, u8p, u8p, C.POINTER(C.c_void_p), C.c_int64, f32p, f64p, C.c_int32, vp, C.c_int32, vp, vp, vp]
-    lib.sgw_act.restype = C.c_int
-    lib.sgw_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
-    lib.sgw_set_option.restype = C.c_int
-    lib.sgw_plan.argtypes = [cfgp, C.c_int32, C.c_int64, C.POINTER(SgwPlan)]
-    lib.sgw_plan.restype = C.c_int
-    lib.sgw_jit_compile.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]
-    lib.sgw_jit_compile.restype = C.c_int
-    lib.sgw_jit_stats.argtypes = [C.POINTER(C.c_double)]
-    lib.sgw_jit_stats.restype = C.c_int
-    lib.sgw_bind_row_tail.argtypes = [vp, C.c_int, C.c_int, vp]
-    lib.sgw_bind_row_tail.restype = C.c_int
-    lib.sgw_turn_bind.argtypes = [vp, C.POINTER(SgwTurnRows)]
-    lib.sgw_turn_bind.restype = C.c_int
-    lib.sgw_turn_set.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
-    lib.sgw_turn_set.restype = C.c_int
-    lib.sgw_turn_begin.argtypes = [vp, u8p, u8p, u8p, f32p, f32p, f64p, C.c_uint32, vp]
-    lib.sgw_turn_begin.restype = C.c_int
-    lib.sgw_turn_act.argtypes = [vp, u8p, u8p, u8p, vp, f32p, f64p, C.c_int32, vp, C.c_int32, vp]
-    lib.sgw_turn_act.restype = C.c_int
-    lib.sgw_turn_begin_rows.argtypes = [vp, u8p, u8p, u8p, f32p, f64p, C.POINTER(C.c_void_p), C.c_int64, C.c_uint32, vp]
-    lib.sgw_turn_begin_rows.restype = C.c_int
-    lib.sgw_turn_act_rows.argtypes = [vp, u8p, u8p, u8p, C.POINTER(C.c_void_p), C.c_int64, f32p, f64p, C.c_int32, vp, C.c_int32, vp]
-    lib.sgw_turn_act_rows.restype = C.c_int
-    lib.sgw_turn_end.argtypes = [vp, vp, vp]
-    lib.sgw_turn_end.restype = C.c_int
-    lib.sgw_turn_state.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), vp]
-    lib.sgw_turn_state.restype = C.c_int
-    lib.sgw_turn_resolve.argtypes = [vp, u8p, u8p, u8p, vp, C.c_int64, f32p, f64p, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp]
-    lib.sgw_turn_resolve.restype = C.c_int
-    lib.sgw_gather_rows.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
-    lib.sgw_gather_rows.restype = C.c_int
-    lib.sgw_verify_rows.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
-    lib.sgw_verify_rows.restype = C.c_int
-    lib.sgw_apply_actions.argtypes = [vp, vp, vp, vp, C.c_int64, vp]
-    lib.sgw_apply_actions.restype = C.c_int
-    lib.sgw_choose_actions.argtypes = [vp, vp, vp, C.c_int64, C.c_uint32, C.c_uint32, vp, vp]
-    lib.sgw_choose_actions.restype = C.c_int
-    lib.sgw_turn_prev_rows.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
-    lib.sgw_turn_prev_rows.restype = C.c_int
-    lib.sgw_turn_epsilon.argtypes = [vp, C.c_int32, C.c_double, vp]
-    lib.sgw_turn_epsilon.restype = C.c_int
-    lib.sgw_render.argtypes = [C.POINTER(SgwRenderDesc), vp]
-    lib.sgw_render.restype = C.c_int
-    lib.sgw_sample.argtypes = [C.POINTER(SgwSampleDesc), vp]
-    lib.sgw_sample.restype = C.c_int
-    lib.sgw_returns.argtypes = [C.POINTER(SgwReturnsDesc), vp]
-    lib.sgw_returns.restype = C.c_int
-    lib.sgw_returns_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.sgw_returns_workspace_bytes.restype = C.c_int64
-    lib.sgw_policy_sample.argtypes = [C.POINTER(SgwPolicyDesc), vp]
-    lib.sgw_policy_sample.restype = C.c_int
-    lib.sgw_turn_policy_sample.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
-    lib.sgw_turn_policy_sample.restype = C.c_int
-    lib.sgw_ppo_loss.argtypes = [C.POINTER(SgwPpoLossDesc), vp]
-    lib.sgw_ppo_loss.restype = C.c_int
-    lib.sgw_ppo_loss_workspace_bytes.argtypes = [C.c_int64]
-    lib.sgw_ppo_loss_workspace_bytes.restype = C.c_int64
-    lib.sgw_iqn_loss.argtypes = [C.POINTER(SgwIqnLossDesc), vp]
-    lib.sgw_iqn_loss.restype = C.c_int
-    lib.sgw_iqn_loss_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.sgw_iqn_loss_workspace_bytes.restype = C.c_int64
-    lib.sgw_iqn_forward.argtypes = [C.POINTER(SgwIqnForwardDesc), vp]
-    lib.sgw_iqn_forward.restype = C.c_int
-    lib.sgw_iqn_forward_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.sgw_iqn_forward_workspace_bytes.restype = C.c_int64
-    lib.sgw_turn_iqn_forward.argtypes = [vp, C.c_int32, C.POINTER(SgwIqnForwardDesc), vp]
-    lib.sgw_turn_iqn_forward.restype = C.c_int
-    lib.sgw_adam_plan_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.sgw_adam_plan_bytes.restype = C.c_int64
-    lib.sgw_adam_plan.argtypes = [C.POINTER(SgwAdamTensor), C.c_int64, C.c_int32, vp, C.c_int64, C.POINTER(SgwAdamPlanInfo)]
-    lib.sgw_adam_plan.restype = C.c_int
-    lib.sgw_adam_step.argtypes = [C.POINTER(SgwAdamStepDesc), vp]
-    lib.sgw_adam_step.restype = C.c_int
-    lib.sgw_last_error.argtypes = []
-    lib.sgw_last_error.restype = C.c_char_p
-    lib.sgw_version.argtypes = []
-    lib.sgw_version.restype = C.c_char_p
-    _lib = lib
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib, _torch = lib, torch
     # tools pass dispatcher options to child processes as SGW_OPTIONS="key=value,key=value": read HERE, by the Python
     # tooling -- the library itself reads no environment variable except SGW_DEBUG
     for item in filter(None, os.environ.get("SGW_OPTIONS", "").replace(";", ",").split(",")):
@@ -553,6 +482,50 @@ def jit_stats() -> dict:
     check(load().sgw_jit_stats(buf))
     return dict(compiled=int(buf[0]), disk_hits=int(buf[1]), mem_hits=int(buf[2]), failed=int(buf[3]),
                 compile_ms=float(buf[4]), load_ms=float(buf[5]))
+
+
+_functions = {}     # launch(): the library's functions by name, looked up once (the small shapes are bound by the host)
+
+
+def launch(name: str, desc, device, *leading) -> None:
+    """One descriptor call ``name(*leading, &desc, stream)`` on ``device``'s current stream, with ``device`` current for it (the library
+    launches on the current device; the descriptor's pointers and the stream belong to ``device``).  As ``GridEngine`` does it: the raw
+    stream handle, and no device switch where ``device`` is current already."""
+    fn = _functions.get(name)
+    if fn is None:
+        fn = _functions[name] = getattr(load(), name)
+    cuda = _torch.cuda
+    current = cuda.current_device()
+    index = current if device.index is None else device.index
+    raw = getattr(_torch._C, "_cuda_getCurrentRawStream", None)
+    stream = C.c_void_p(raw(index) if raw is not None else cuda.current_stream(index).cuda_stream)
+    if index == current:
+        code = fn(*leading, C.byref(desc), stream)
+    else:
+        with cuda.device(index):
+            code = fn(*leading, C.byref(desc), stream)
+    if code:
+        check(code)
+
+
+def workspace(nbytes: int, device):
+    """The float64 tensor a descriptor's ``workspace`` / ``workspace_bytes`` point at: ``nbytes`` (what a ``sgw_*_workspace_bytes`` gave:
+    a negative value is its error code) rounded up, at least one element."""
+    import torch
+
+    if nbytes < 0:
+        check(int(nbytes))
+    return torch.empty((max((int(nbytes) + 7) // 8, 1),), dtype=torch.float64, device=device)
+
+
+def float_code(dtype) -> int:
+    """``POLICY_F32`` / ``POLICY_F64`` of a float tensor's torch dtype (every descriptor's ``*_type`` of a float tensor), by its width."""
+    return POLICY_F64 if dtype.itemsize == 8 else POLICY_F32
+
+
+def action_code(dtype) -> int:
+    """``PPO_ACT_I64`` / ``PPO_ACT_U8`` of an action tensor's torch dtype (the losses' ``action_type``), by its width."""
+    return PPO_ACT_U8 if dtype.itemsize == 1 else PPO_ACT_I64
 
 
 def check(rc: int) -> None:

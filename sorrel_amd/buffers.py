@@ -85,8 +85,6 @@ def _check_index_list(name, values, batch_size, bound, device):
 
 def _launch_sample(layout, n_frames, batch_size, outs, index, starts, envs, num_starts, count=None, seed=0):
     """One ``sgw_sample`` call on the current stream.  ``outs`` = (states, next_states, actions, rewards, dones, valid) tensors."""
-    import ctypes as C
-
     from sorrel_amd import _native as N
 
     d = N.SgwSampleDesc()
@@ -103,7 +101,7 @@ def _launch_sample(layout, n_frames, batch_size, outs, index, starts, envs, num_
     d.scalar_turn_stride, d.scalar_env_stride = layout["cstr"]
     d.seed, d.draw = seed & 0xFFFFFFFFFFFFFFFF, 0
     d.n_frames, d.src_type, d.act_type = n_frames, layout["src"], layout["act"]
-    N.check(N.load().sgw_sample(C.byref(d), C.c_void_p(torch.cuda.current_stream(layout["device"]).cuda_stream)))
+    N.launch("sgw_sample", d, layout["device"])
 
 
 def _sample_outputs(batch_size, n_frames, R, device):
@@ -153,8 +151,7 @@ class Returns:
             self.mean = self._stats[..., 0].view(shape[1:] if normalize == "column" else ())
             self.std = self._stats[..., 1].view(shape[1:] if normalize == "column" else ())
         if normalize == "all" and torch.device(device).type == "cuda":
-            need = int(N.load().sgw_returns_workspace_bytes(max(int(shape[0]), 1), cols))
-            self._workspace = torch.empty((need // 8,), dtype=torch.float64, device=device)
+            self._workspace = N.workspace(N.load().sgw_returns_workspace_bytes(max(int(shape[0]), 1), cols), device)
 
     def __repr__(self):
         return f"Returns(shape={tuple(self.returns.shape)}, normalize={self._mode!r})"
@@ -218,8 +215,6 @@ def _returns_views(ring, agent):
 
 def _ring_returns(ring, agent, gamma, normalize, first, count, dtype, out):
     """``returns()`` of both ring classes: the segment's defaults and bounds, then ``sgw_returns`` (device ring) or ``_returns_torch``."""
-    import ctypes as C
-
     cap = ring.capacity
     full = ring.size >= cap
     if first is None:
@@ -250,7 +245,7 @@ def _ring_returns(ring, agent, gamma, normalize, first, count, dtype, out):
     d.gamma = float(gamma)
     d.normalize = {None: N.RETURNS_NORM_NONE, "column": N.RETURNS_NORM_COLUMN, "all": N.RETURNS_NORM_ALL}[normalize]
     d.out_type = N.RETURNS_OUT_F32 if dtype == torch.float32 else N.RETURNS_OUT_F64
-    N.check(N.load().sgw_returns(C.byref(d), C.c_void_p(torch.cuda.current_stream(ring.device).cuda_stream)))
+    N.launch("sgw_returns", d, ring.device)
     return res
 
 

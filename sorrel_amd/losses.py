@@ -26,10 +26,10 @@ outputs and ``loss.backward()``) has the same three forms -- ``iqn_loss_terms`` 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
+from sorrel_amd import _native as N
+from sorrel_amd._check import check_tensors
 from sorrel_amd.models.base_model import ActionProbs
 
 _FLOATS = (torch.float32, torch.float64)
@@ -52,10 +52,7 @@ class PPOLoss:
         self.row_terms = torch.empty((n, 3), dtype=torch.float64, device=dev) if row_terms else None
         self._workspace = None
         if dev.type == "cuda":
-            from sorrel_amd import _native as N
-
-            need = int(N.load().sgw_ppo_loss_workspace_bytes(n))
-            self._workspace = torch.empty((max(need, 8) // 8,), dtype=torch.float64, device=dev)
+            self._workspace = N.workspace(N.load().sgw_ppo_loss_workspace_bytes(n), dev)
 
     def __repr__(self):
         return f"PPOLoss(n={self.grad_values.numel()}, num_actions={self.grad_dist.shape[1]})"
@@ -72,18 +69,8 @@ def _check(t, values, actions, old_log_probs, returns):
     n, na = int(t.shape[0]), int(t.shape[1])
     if t.stride(1) != 1 and na > 1 or (n > 1 and t.stride(0) < na):
         raise ValueError(f"the distribution's rows must be contiguous (strides {tuple(t.stride())})")
-    for name, x, dtypes in (("values", values, _FLOATS), ("actions", actions, (torch.int64, torch.uint8)),
-                            ("old_log_probs", old_log_probs, (torch.float32,)), ("returns", returns, _FLOATS)):
-        if not torch.is_tensor(x):
-            raise TypeError(f"{name} must be a tensor, not {type(x).__name__}")
-        if x.dtype not in dtypes:
-            raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, not {x.dtype}")
-        if x.numel() != n:
-            raise ValueError(f"{name} has {x.numel()} elements for {n} rows of the distribution")
-        if not x.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if x.device != t.device:
-            raise ValueError(f"{name} is on {x.device}, the distribution on {t.device}")
+    check_tensors(t.device, "the distribution", ("values", values, _FLOATS, n), ("actions", actions, (torch.int64, torch.uint8), n),
+                  ("old_log_probs", old_log_probs, (torch.float32,), n), ("returns", returns, _FLOATS, n))
     return n, na
 
 
@@ -161,8 +148,6 @@ def ppo_loss_terms(dist, values, actions, old_log_probs, returns, eps_clip, entr
     if n == 0:
         res.terms.fill_(float("nan"))                        # the mean of nothing, as torch's
         return res
-    from sorrel_amd import _native as N
-
     d = N.SgwPpoLossDesc()
     d.dist, d.values, d.actions, d.old_log_probs, d.returns = t.data_ptr(), values.data_ptr(), actions.data_ptr(), old_log_probs.data_ptr(), returns.data_ptr()
     d.out_grad_dist, d.out_grad_values, d.out_terms = res.grad_dist.data_ptr(), res.grad_values.data_ptr(), res.terms.data_ptr()
@@ -171,12 +156,9 @@ def ppo_loss_terms(dist, values, actions, old_log_probs, returns, eps_clip, entr
     d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
     d.n, d.row_stride, d.num_actions = n, (int(t.stride(0)) if n > 1 else na), na
     d.eps_clip, d.entropy_coef, d.value_coef = eps_clip, entropy_coef, value_coef
-    f = {torch.float32: N.POLICY_F32, torch.float64: N.POLICY_F64}
-    d.dist_type, d.mode = f[t.dtype], (N.POLICY_LOGITS if logits else N.POLICY_PROBS)
-    d.value_type, d.returns_type = f[values.dtype], f[returns.dtype]
-    d.action_type = N.PPO_ACT_U8 if actions.dtype == torch.uint8 else N.PPO_ACT_I64
-    with torch.cuda.device(t.device):
-        N.check(N.load().sgw_ppo_loss(C.byref(d), C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
+    d.dist_type, d.mode = N.float_code(t.dtype), (N.POLICY_LOGITS if logits else N.POLICY_PROBS)
+    d.value_type, d.returns_type, d.action_type = N.float_code(values.dtype), N.float_code(returns.dtype), N.action_code(actions.dtype)
+    N.launch("sgw_ppo_loss", d, t.device)
     return res
 
 
@@ -219,19 +201,16 @@ class IQNLoss:
 
     def __init__(self, q_expected, row_terms=False, td_error=False):
         dev = q_expected.device
-        B, N, _A = (int(s) for s in q_expected.shape)
+        B, Nq, _A = (int(s) for s in q_expected.shape)
         self.terms = torch.empty((1,), dtype=torch.float64, device=dev)
         self.loss = self.terms[0]
         self.grad_expected = torch.empty(q_expected.shape, dtype=torch.float32, device=dev)
         self.next_actions = torch.empty((B,), dtype=torch.int64, device=dev)
         self.row_terms = torch.empty((B,), dtype=torch.float64, device=dev) if row_terms else None
-        self.td_error = torch.empty((B, N, N), dtype=torch.float32, device=dev) if td_error else None
+        self.td_error = torch.empty((B, Nq, Nq), dtype=torch.float32, device=dev) if td_error else None
         self._workspace = None
         if dev.type == "cuda":
-            from sorrel_amd import _native as N_
-
-            need = int(N_.load().sgw_iqn_loss_workspace_bytes(B, N))
-            self._workspace = torch.empty((max(need, 8) // 8,), dtype=torch.float64, device=dev)
+            self._workspace = N.workspace(N.load().sgw_iqn_loss_workspace_bytes(B, Nq), dev)
 
     def __repr__(self):
         return f"IQNLoss(n={self.grad_expected.shape[0]}, num_quantiles={self.grad_expected.shape[1]}, num_actions={self.grad_expected.shape[2]})"
@@ -244,32 +223,23 @@ def _check_iqn(q_expected, taus, q_next_local, q_next_target, actions, rewards, 
             raise TypeError(f"{name} must be a tensor, not {type(x).__name__}")
     if q_expected.dim() != 3:
         raise ValueError(f"q_expected must be [B, N, A], not {tuple(q_expected.shape)}")
-    B, N, A = (int(s) for s in q_expected.shape)
-    if not 1 <= N <= 64:
-        raise ValueError(f"{N} quantiles: the loss takes 1..64")
-    if not 1 <= A <= 256:
-        raise ValueError(f"{A} actions: the loss takes 1..256")
+    B, Nq, A = (int(s) for s in q_expected.shape)
+    if not 1 <= Nq <= N.IQN_MAX_QUANTILES:
+        raise ValueError(f"{Nq} quantiles: the loss takes 1..{N.IQN_MAX_QUANTILES}")
+    if not 1 <= A <= N.POLICY_MAX_ACTIONS:
+        raise ValueError(f"{A} actions: the loss takes 1..{N.POLICY_MAX_ACTIONS}")
     f32 = (torch.float32,)
-    for name, x, dtypes, shapes in (
-            ("q_expected", q_expected, f32, ((B, N, A),)), ("q_next_local", q_next_local, f32, ((B, N, A),)),
-            ("q_next_target", q_next_target, f32, ((B, N, A),)), ("taus", taus, f32, ((B, N, 1), (B, N))),
-            ("actions", actions, (torch.int64, torch.uint8), ((B, 1), (B,))), ("rewards", rewards, f32, ((B, 1), (B,))),
-            ("dones", dones, f32, ((B, 1), (B,))), ("valid", valid, _FLOATS, ((B, 1), (B,)))):
-        if x.dtype not in dtypes:
-            raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, not {x.dtype}")
-        if tuple(x.shape) not in shapes:
-            raise ValueError(f"{name} has shape {tuple(x.shape)}; expected {' or '.join(str(list(s)) for s in shapes)}")
-        if not x.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if x.device != q_expected.device:
-            raise ValueError(f"{name} is on {x.device}, q_expected on {q_expected.device}")
-    return B, N, A
+    full, row = ((B, Nq, A),), ((B, 1), (B,))
+    check_tensors(q_expected.device, "q_expected",
+                  ("q_expected", q_expected, f32, full), ("q_next_local", q_next_local, f32, full), ("q_next_target", q_next_target, f32, full),
+                  ("taus", taus, f32, ((B, Nq, 1), (B, Nq))), ("actions", actions, (torch.int64, torch.uint8), row), ("rewards", rewards, f32, row),
+                  ("dones", dones, f32, row), ("valid", valid, _FLOATS, row))
+    return B, Nq, A
 
 
 def _check_iqn_out(out, q_expected, row_terms, td_error):
     if not isinstance(out, IQNLoss):
         raise TypeError("out= takes an earlier IQNLoss")
-    B, N, _A = (int(s) for s in q_expected.shape)
     tensors = [out.terms, out.grad_expected, out.next_actions] + [x for x in (out.row_terms, out.td_error, out._workspace) if x is not None]
     if (out.grad_expected.shape != q_expected.shape or any(x.device != q_expected.device for x in tensors)
             or (row_terms and out.row_terms is None) or (td_error and out.td_error is None)
@@ -319,7 +289,7 @@ def iqn_loss_terms(q_expected, taus, q_next_local, q_next_target, actions, rewar
     and ``discount`` is ``GAMMA ** n_step``.  Returns an ``IQNLoss``.  On a HIP device this is one ``sgw_iqn_loss`` call; with ``out=``
     (an earlier result for the same shapes) it allocates nothing and does not synchronise, so it can be recorded into a graph.  A row
     whose action is out of range gives NaN for its term, its gradient row and the loss."""
-    B, N, A = _check_iqn(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid)
+    B, Nq, A = _check_iqn(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid)
     discount = float(discount)
     if discount != discount or discount in (float("inf"), float("-inf")):
         raise ValueError(f"discount = {discount} must be finite")
@@ -329,9 +299,7 @@ def iqn_loss_terms(q_expected, taus, q_next_local, q_next_target, actions, rewar
     if B == 0:
         res.terms.fill_(float("nan"))                        # the mean of nothing, as torch's
         return res
-    from sorrel_amd import _native as N_
-
-    d = N_.SgwIqnLossDesc()
+    d = N.SgwIqnLossDesc()
     d.q_next_local, d.q_next_target, d.q_expected, d.taus = q_next_local.data_ptr(), q_next_target.data_ptr(), q_expected.data_ptr(), taus.data_ptr()
     d.actions, d.rewards, d.dones, d.valid = actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(), valid.data_ptr()
     d.out_terms, d.out_grad_expected, d.out_next_actions = res.terms.data_ptr(), res.grad_expected.data_ptr(), res.next_actions.data_ptr()
@@ -340,11 +308,9 @@ def iqn_loss_terms(q_expected, taus, q_next_local, q_next_target, actions, rewar
     if td_error:
         d.out_td_error = res.td_error.data_ptr()
     d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
-    d.n, d.num_quantiles, d.num_actions, d.discount = B, N, A, discount
-    d.action_type = N_.PPO_ACT_U8 if actions.dtype == torch.uint8 else N_.PPO_ACT_I64
-    d.valid_type = N_.POLICY_F64 if valid.dtype == torch.float64 else N_.POLICY_F32
-    with torch.cuda.device(q_expected.device):
-        N_.check(N_.load().sgw_iqn_loss(C.byref(d), C.c_void_p(torch.cuda.current_stream(q_expected.device).cuda_stream)))
+    d.n, d.num_quantiles, d.num_actions, d.discount = B, Nq, A, discount
+    d.action_type, d.valid_type = N.action_code(actions.dtype), N.float_code(valid.dtype)
+    N.launch("sgw_iqn_loss", d, q_expected.device)
     return res
 
 

@@ -10,7 +10,6 @@ parameter and buffer names and shapes so that its ``state_dict`` loads, and the 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence
 
@@ -19,10 +18,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from sorrel_amd import _native as N_
 from sorrel_amd.models.base_model import BaseModel
 
-N_COS = 64
-MAX_LAYER, MAX_QUANTILES, MAX_ACTIONS = 256, 64, 64
+N_COS, MAX_LAYER, MAX_QUANTILES, MAX_ACTIONS = N_.IQN_N_COS, N_.IQN_MAX_LAYER, N_.IQN_MAX_QUANTILES, N_.IQN_MAX_ACTIONS    # (the header's)
 
 
 class NoisyLinear(nn.Linear):
@@ -73,7 +72,7 @@ class IQNOutput:
         self.taus = torch.empty((B, N, 1), dtype=torch.float32, device=device)
         self.qvalues = torch.empty((B, A), dtype=torch.float32, device=device)
         self.cos = torch.empty((B, N, N_COS), dtype=torch.float32, device=device) if cos else None
-        self._workspace = torch.empty((max(B * L, 1),), dtype=torch.float32, device=device)
+        self._workspace = N_.workspace(4 * B * L, device)       # (float32 [B, L])
         self._weights = None                  # training mode: where the effective noisy weights are composed (fixed addresses)
 
     def __repr__(self):
@@ -195,7 +194,7 @@ class IQN(nn.Module):
         else:
             if not isinstance(out, IQNOutput):
                 raise TypeError("out= takes an earlier IQNOutput")
-            if tuple(out.quantiles.shape) != (B, N, A) or out.quantiles.device != dev or out._workspace.numel() < B * L or (cos and out.cos is None):
+            if tuple(out.quantiles.shape) != (B, N, A) or out.quantiles.device != dev or out._workspace.numel() * 8 < 4 * B * L or (cos and out.cos is None):
                 raise ValueError("out= was made for other shapes or another device, or without the optional outputs asked for")
             res = out
         if dev.type != "cuda":
@@ -206,18 +205,16 @@ class IQN(nn.Module):
                 raise TypeError("the network's parameters must be contiguous float32")
         if B == 0:
             return res
-        from sorrel_amd import _native as N_
-
         d = N_.SgwIqnForwardDesc()
         d.states = flat.data_ptr()
         (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
         d.out_qvalues, d.out_quantiles, d.out_taus = res.qvalues.data_ptr(), res.quantiles.data_ptr(), res.taus.data_ptr()
         if res.cos is not None and cos:
             d.out_cos = res.cos.data_ptr()
-        d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 4
+        d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
         d.n, d.state_stride = B, int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), flat.shape[1])
         d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = flat.shape[1], L, N, A, N_COS
-        d.state_type = 1 if flat.dtype == torch.uint8 else 0
+        d.state_type = N_.IQN_STATE_U8 if flat.dtype == torch.uint8 else N_.IQN_STATE_F32
         keep = None
         if taus is not None:
             d.taus = taus.data_ptr()
@@ -233,14 +230,12 @@ class IQN(nn.Module):
                 if keep.dtype != torch.int64 or tuple(keep.shape) != (B,) or not keep.is_contiguous() or keep.device != dev:
                     raise ValueError(f"key['idx'] must be contiguous int64 [{B}] on {dev}")
                 d.idx = keep.data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with torch.cuda.device(dev):
-            if engine is not None and taus is None:
-                if B != engine.num_envs:
-                    raise ValueError(f"the turn protocol's rows are the engine's {engine.num_envs} envs; got {B}")
-                N_.check(N_.load().sgw_turn_iqn_forward(engine._h, int(agent or 0), C.byref(d), stream))
-            else:
-                N_.check(N_.load().sgw_iqn_forward(C.byref(d), stream))
+        if engine is not None and taus is None:
+            if B != engine.num_envs:
+                raise ValueError(f"the turn protocol's rows are the engine's {engine.num_envs} envs; got {B}")
+            N_.launch("sgw_turn_iqn_forward", d, dev, engine._h, int(agent or 0))
+        else:
+            N_.launch("sgw_iqn_forward", d, dev)
         return res
 
     def _quantiles_by_torch(self, flat, N, taus, res):

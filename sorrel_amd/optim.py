@@ -151,14 +151,11 @@ class FusedAdam(torch.optim.Optimizer):
             self._key = key
         from sorrel_amd import _native as N
 
-        lib = N.load()
-        stream = C.c_void_p(torch.cuda.current_stream(active[0][0].device).cuda_stream)
-        with torch.cuda.device(active[0][0].device):
-            for tb in self._tables:
-                tb.desc.step = 0 if tb.state is not None else tb.step + 1
-                N.check(lib.sgw_adam_step(C.byref(tb.desc), stream))
-                tb.step += 1
-                tb.pending += 1
+        for tb in self._tables:
+            tb.desc.step = 0 if tb.state is not None else tb.step + 1
+            N.launch("sgw_adam_step", tb.desc, active[0][0].device)
+            tb.step += 1
+            tb.pending += 1
         return self._tables[0].norm if self.max_grad_norm is not None else None
 
     def _step_torch(self, params):
@@ -214,7 +211,7 @@ class FusedAdam(torch.optim.Optimizer):
                 r.param, r.grad, r.exp_avg, r.exp_avg_sq = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                 r.target = t.data_ptr() if t is not None else None
                 r.numel, r.lr = p.numel(), lr
-            code = N.POLICY_F64 if dtype == torch.float64 else N.POLICY_F32
+            code = N.float_code(dtype)
             size = lib.sgw_adam_plan_bytes(T, sum(p.numel() for p, _, _ in members))
             if size < 0:
                 N.check(int(size))
@@ -224,7 +221,7 @@ class FusedAdam(torch.optim.Optimizer):
             tb = _Table()
             tb.params, tb.step, tb.pending = [p for p, _, _ in members], step, 0
             tb.image = torch.from_numpy(host).to(dev)
-            tb.workspace = torch.empty((max(1, info.num_chunks),), dtype=torch.float64, device=dev)
+            tb.workspace = N.workspace(info.workspace_bytes, dev)
             tb.out_norm = torch.zeros((2,), dtype=torch.float64, device=dev)
             tb.norm = tb.out_norm[0]
             tb.state = None

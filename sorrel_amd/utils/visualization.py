@@ -295,10 +295,7 @@ class SpriteRenderer:
         d.n_tiles, d.th, d.tw = int(a.tiles.shape[0]), th, tw
         d.k, d.vision, d.oob_tile = k, int(vision), int(a.oob_tile)
         d.mode = N.RENDER_LAYERS if per_layer else N.RENDER_COMPOSITE
-        import ctypes as C
-
-        with torch.cuda.device(dev):
-            N.check(N.load().sgw_render(C.byref(d), torch.cuda.current_stream(dev).cuda_stream))
+        N.launch("sgw_render", d, dev)
         return out
 
     def frames(self, env_ids=None, out=None) -> torch.Tensor:

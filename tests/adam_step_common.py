@@ -23,10 +23,14 @@ from __future__ import annotations
 
 import ctypes
 import ctypes.util
+import functools
 import json
 import os
 
 import numpy as np
+
+from tests import learner_common as LK
+from tests.learner_common import bits, tree  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE_DIR = os.path.join(HERE, "golden", "adam_step")
@@ -55,30 +59,10 @@ def fma(a, b, c, dtype):
     return np.asarray((_fma32 if dtype == np.float32 else _fma64)(a, b, c), dtype=dtype).reshape(a.shape)
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def same_bits(got, want, what, ctx=""):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (ctx, what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{ctx} {what}: {int(bad.sum())} of {bad.size} elements differ; the first at {np.argwhere(bad)[0].tolist()}: " \
-                          f"{got[bad][0]!r} != {want[bad][0]!r}"
+same_bits = functools.partial(LK.same_bits, nan_payloads=True)      # (an optimiser's state: a NaN's payload counts as well)
 
 
 # ------------------------------------------------------------------------------------------------------------- the norm's order
-def tree(lanes):
-    red = np.array(lanes, np.float64)
-    assert red.shape == (BLOCK,)
-    s = BLOCK // 2
-    while s:
-        red[:s] = red[:s] + red[s:2 * s]
-        s //= 2
-    return red[0]
-
-
 def chunk_sum(g):
     """S of one chunk: lane t adds the squares of elements 4 (t + 256 r) + e, r = 0..3, e = 0..3, in that order; then the tree."""
     g = np.asarray(g).reshape(-1)
@@ -91,7 +75,7 @@ def chunk_sum(g):
         for r in range(4):
             for e in range(4):
                 acc = acc + sq[r, :, e]
-        return tree(acc)
+        return tree(acc[None, :])[0]
 
 
 def chunks_of(numel: int) -> int:
@@ -125,7 +109,7 @@ def merge(sums):
     with np.errstate(all="ignore"):
         for k, s in enumerate(sums):
             lanes[k % BLOCK] = lanes[k % BLOCK] + s
-        return tree(lanes)
+        return tree(lanes[None, :])[0]
 
 
 def grad_norm(grads) -> float:

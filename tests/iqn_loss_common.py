@@ -16,19 +16,18 @@ Branches -- which action is the maximum, which side of ``|td| = 1`` -- are not c
 around every one of them outside the hand-made set, whose values are dyadic so that every order gives the same bits."""
 import json
 import os
-import re
 
 import numpy as np
 
 from tests import helpers as H
+from tests import learner_common as LK
+from tests.learner_common import BLOCK, bits, same_bits, tree  # noqa: F401
 
 FIXTURE = os.path.join(H.ROOT, "tests", "golden", "iqn_loss", "quantile_huber.npz")
-BLOCK = 256                   # threads of a workgroup (kBlock)
 
 
 def max_blocks():
-    text = open(os.path.join(H.ROOT, "sorrel_amd", "csrc", "iqn_loss.h")).read()
-    return int(re.search(r"kIqnMaxBlocks = (\d+);", text)[1])
+    return LK.max_blocks("iqn_loss.h", "kIqnMaxBlocks")
 
 
 def group(N):
@@ -68,15 +67,6 @@ def batch_sum(S, N):
             chunk = parts[start:start + BLOCK]
             merged[0, :chunk.shape[0]] = merged[0, :chunk.shape[0]] + chunk
         return float(tree(merged)[0])
-
-
-def tree(red):
-    red = red.copy()
-    s = BLOCK // 2
-    while s > 0:
-        red[:, :s] = red[:, :s] + red[:, s:2 * s]
-        s //= 2
-    return red[:, 0]
 
 
 def first_max(m):
@@ -147,24 +137,6 @@ def tolerances(info):
         count = B * N * N
         L = count * 2.0 ** -53 * (np.abs(info["ql"]).sum() / max(count, 1))
     return dict(grad=grad, L=float(L))
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({4: np.uint32, 8: np.uint64}[x.dtype.itemsize]) if x.dtype.kind == "f" else x
-
-
-def same_bits(got, want, what, ctx=""):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (ctx, what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype.kind == "f":                                                        # (any NaN is a NaN: payloads are not part of the contract)
-        nan = np.isnan(want)
-        assert np.array_equal(np.isnan(got), nan), (ctx, what, "NaN pattern")
-        a, b = np.where(nan, 0, got), np.where(nan, 0, want)
-        diff = bits(a.astype(got.dtype)) != bits(b.astype(got.dtype))
-    else:
-        diff = got != want
-    assert not diff.any(), (ctx, what, f"{int(diff.sum())} of {diff.size} differ, first at {tuple(np.argwhere(diff)[0])}")
 
 
 def load_fixture():

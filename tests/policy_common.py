@@ -3,12 +3,13 @@ the keyed draw, the running-sum search, torch's clamped log-probability and entr
 (``tests/golden/policy/actor_critic.npz``, written by ``tools/make_policy_golden.py``), float32 ulp distances and descriptor helpers.
 Not collected by pytest."""
 import os
-import re
 
 import numpy as np
 
 from oracle import gridstep_oracle as O
 from tests import helpers as H
+from tests import learner_common as LK
+from tests.learner_common import ulps  # noqa: F401
 
 FIXTURE = os.path.join(H.ROOT, "tests", "golden", "policy", "actor_critic.npz")
 STREAM_POLICY = 10
@@ -17,8 +18,7 @@ MARGIN = 2.0 ** -40           # share of S a threshold must keep from every runn
 
 
 def max_blocks():
-    text = open(os.path.join(H.ROOT, "sorrel_amd", "csrc", "policy.h")).read()
-    return int(re.search(r"kPolicyMaxBlocks = (\d+);", text)[1])
+    return LK.max_blocks("policy.h", "kPolicyMaxBlocks")
 
 
 def draws(seed, first_env, env, epoch, turn, agent):
@@ -79,20 +79,6 @@ def margin(info):
     """The smallest distance of a row's threshold from any of its running sums, as a share of S (valid rows)."""
     ok = ~info["bad"]
     return (np.abs(info["c"][ok] - info["t"][ok, None]).min(axis=1) / info["S"][ok]).min() if ok.any() else np.inf
-
-
-def ulps(a, b):
-    """Distance of float32 arrays in units in the last place (NaN against NaN: 0; NaN against a number: a huge count)."""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-
-    def ordered(v):
-        i = v.view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-
-    d = np.abs(ordered(a) - ordered(b))
-    both = np.isnan(a) & np.isnan(b)
-    one = np.isnan(a) ^ np.isnan(b)
-    return np.where(both, 0, np.where(one, 1 << 40, d))
 
 
 def load_fixture():

@@ -20,11 +20,11 @@ not covered by a tolerance: the fixture's generator asserts margins of ``2^-40``
 GPU tests assert the same on the restatement before they compare."""
 import json
 import os
-import re
 
 import numpy as np
 
 from tests import helpers as H
+from tests import learner_common as LK
 
 FIXTURE = os.path.join(H.ROOT, "tests", "golden", "ppo_loss", "clip_loss.npz")
 U = 2.0 ** -53
@@ -35,8 +35,7 @@ EPS_LO, EPS_HI = 2.0 ** -52, 1.0 - 2.0 ** -52
 
 
 def max_blocks():
-    text = open(os.path.join(H.ROOT, "sorrel_amd", "csrc", "ppo_loss.h")).read()
-    return int(re.search(r"kPpoMaxBlocks = (\d+);", text)[1])
+    return LK.max_blocks("ppo_loss.h", "kPpoMaxBlocks")
 
 
 def restate(x, logits, values, actions, old, returns, eps_clip, entropy_coef, value_coef=0.5):

@@ -9,6 +9,7 @@ import re
 import numpy as np
 
 from tests import helpers as H
+from tests import learner_common as LK
 
 FIXTURE = os.path.join(H.ROOT, "tests", "golden", "returns", "ppo_returns.npz")
 UNIT = np.float32(0.37)
@@ -21,8 +22,7 @@ def chunk():
 
 
 def max_blocks():
-    text = open(os.path.join(H.ROOT, "sorrel_amd", "csrc", "returns.h")).read()
-    return int(re.search(r"kReturnsMaxBlocks = (\d+);", text)[1])
+    return LK.max_blocks("returns.h", "kReturnsMaxBlocks")
 
 
 def load_fixture():

@@ -1,14 +1,14 @@
-"""CPU tests of the drop-in boundary: the C-ABI library loads, exports every symbol
-include/sgw.h declares, and the ctypes mirror of sgw_config has the C layout.
+"""CPU tests of the drop-in boundary: the C-ABI library loads and exports every symbol include/sgw.h declares, and the whole ctypes
+binding agrees with the header -- every struct mirror's layout, every function's prototype, every constant.
 No compute calls are made (there is no GPU in the build container)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
 from tests import helpers as H
+from tests import learner_common as LK
 from sorrel_amd import _native as N
 
 HEADER = os.path.join(H.ROOT, "include", "sgw.h")
@@ -24,20 +24,79 @@ def test_header_declares_what_binding_expects():
     assert set(declared_symbols()) == set(N.EXPORTS)
 
 
-def test_flag_constants_match_the_header():
-    """The ctypes binding's flag / rule constants are the header's macros (the header is the interface)."""
-    text = open(HEADER).read()
-    macros = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(\d+)u?\b", text)}
-    for name in ("STEP_SWEEP", "STEP_RANDOM_ACTIONS", "STEP_NO_OBS", "STEP_OBS_NEXT", "STEP_OBS_NEXT_PACKED", "STEP_NO_MOVE", "STEP_OBS_AGENT_MAJOR", "CAP_OBSERVE_ROWS", "CAP_ACT", "CAP_RESOLVE", "CAP_OBS_AGENT_MAJOR", "CAP_SWEEP_ROWS"):
-        assert getattr(N, name) == macros["SGW_" + name], name
-    flags = [macros[k] for k in macros if k.startswith("SGW_STEP_") and k != "SGW_STEP_DEFAULT"]
-    assert len(set(flags)) == len(flags) and all(f & (f - 1) == 0 for f in flags)      # distinct single bits
-    for name in ("ACT_U8", "ACT_I32", "ACT_I64", "ACT_QF32", "TAIL_NONE", "TAIL_AGENT_IS_IT", "TAIL_POSITION_TABLE"):
-        assert getattr(N, name) == macros["SGW_" + name], name
+def header_macros():
+    """Every numeric macro of the header: ``{"SGW_X": value}`` (decimal or hex, an ``u`` suffix and parentheses allowed)."""
+    return {m.group(1): int(m.group(2), 0)
+            for m in re.finditer(r"^#define\s+(SGW_[A-Z_0-9]+)\s+\(?(-?(?:0x[0-9A-Fa-f]+|\d+))u?\)?(?=\s)", open(HEADER).read(), flags=re.M)}
+
+
+# numeric macros of the header the binding has no name for, and why
+UNMIRRORED = {"SGW_STREAM_" + name: "a stream only the kernels and the oracle draw from (its number is checked against the oracle's below)"
+              for name in ("SPAWN", "SPAWN_KIND", "ACTION", "PLACE", "DENSE", "DENSE_KIND", "TAG_INIT", "EXPLORE")}
+
+
+def test_constants_match_the_header():
+    """The binding's constants are the header's macros (the header is the interface): every ``SGW_<NAME>`` whose ``<NAME>`` the binding
+    has holds the header's value, and every other numeric macro is on ``UNMIRRORED`` with its reason."""
+    macros = header_macros()
+    assert len(macros) >= 97
+    for name, value in macros.items():
+        if hasattr(N, name[4:]):
+            assert getattr(N, name[4:]) == value, name
+    assert {name for name in macros if not hasattr(N, name[4:])} == set(UNMIRRORED)
+    flags = [macros[k] for k in macros if k.startswith("SGW_STEP_")]
+    assert len(set(flags)) == len(flags) == 7 and all(f & (f - 1) == 0 for f in flags)      # distinct single bits
     # the counter-RNG streams: the oracle's numbering is the header's (tests compare draws made by either)
     from oracle import gridstep_oracle as O
     for name in ("SPAWN", "SPAWN_KIND", "ACTION", "PLACE", "DENSE", "DENSE_KIND", "TAG_INIT", "EXPLORE"):
         assert getattr(O, "STREAM_" + name) == macros["SGW_STREAM_" + name], name
+
+
+def _c_kind(decl):
+    """An argument or return type of the header as what the calling convention sees: pointer, double, or an integer's width."""
+    if "*" in decl:
+        return "pointer"
+    words = decl.replace("const", "").split()
+    return {"double": "double", "int64_t": "int64", "int32_t": "int32", "uint32_t": "int32", "int": "int32", "void": None}[words[0]]
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return None
+    if t in (C.c_void_p, C.c_char_p) or hasattr(t, "contents"):
+        return "pointer"
+    return "double" if t is C.c_double else {4: "int32", 8: "int64"}[C.sizeof(t)]
+
+
+def test_prototypes_match_the_header():
+    """Every function of the binding's table against the header's declaration: the argument count, per argument pointer / double /
+    4-byte / 8-byte integer, and the return type."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = {name: (ret, [a for a in args.split(",") if a.strip() != "void"])
+                for ret, name, args in re.findall(r"([A-Za-z_][\w \*]*?)\b(sgw_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text)}
+    assert set(declared) == set(N.PROTOTYPES) == set(N.EXPORTS) and len(declared) >= 67
+    for name, (restype, argtypes) in N.PROTOTYPES.items():
+        ret, args = declared[name]
+        assert [_ctypes_kind(t) for t in argtypes] == [_c_kind(a) for a in args], name
+        assert _ctypes_kind(restype) == _c_kind(ret), name
+        if "*" not in ret:
+            assert restype is {"int": C.c_int, "int64_t": C.c_int64, "void": None}[ret.strip()], name
+        assert all(t not in (C.c_float, C.c_longdouble) for t in argtypes), name
+
+
+def test_load_sets_every_prototype(built):
+    lib = N.load()
+    for name, (restype, argtypes) in N.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_workspace_raises_for_an_error_code_and_holds_at_least_one_element(built):
+    lib = N.load()
+    assert lib.sgw_ppo_loss_workspace_bytes(-1) == N.EINVAL
+    with pytest.raises(ValueError, match="n ="):
+        N.workspace(lib.sgw_ppo_loss_workspace_bytes(-1), "cpu")
+    assert [N.workspace(n, "cpu").numel() for n in (0, 1, 8, 9, 24)] == [1, 1, 1, 2, 3]
 
 
 def test_value_action_is_argmax_or_the_engines_uniform_draw():
@@ -80,18 +139,27 @@ def test_library_has_gfx950_code_object(built):
     assert b"step_kernel" in data
 
 
-def test_config_struct_layout_matches_c(tmp_path):
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in N.SgwConfig._fields_]
-    body = "".join(f'printf("{f} %zu\\n", offsetof(sgw_config, {f}));\n' for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sgw.h"\nint main(){\n'
-                   'printf("sizeof %zu\\n", sizeof(sgw_config));\n' + body + "return 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(H.ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(N.SgwConfig)
-    for f in fields:
-        assert int(out[f]) == getattr(N.SgwConfig, f).offset, f
+def test_every_struct_layout_matches_c(tmp_path):
+    """Every ``ctypes.Structure`` of the binding (found by introspection: a new mirror is covered as it is added) against the C
+    compiler's view of the struct its docstring names: ``sizeof``, ``offsetof`` of every field, and the field names in the header's
+    declaration order.  One compile for all of them."""
+    mirrors = {}
+    for cls in vars(N).values():
+        if isinstance(cls, type) and issubclass(cls, C.Structure) and cls is not C.Structure:
+            named = re.search(r"``struct (sgw_\w+)``", cls.__doc__ or "")
+            assert named, f"{cls.__name__}'s docstring does not name the struct it mirrors"
+            mirrors[named.group(1)] = cls
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    bodies = dict(re.findall(r"typedef struct (sgw_\w+) \{(.*?)\} \1;", text, flags=re.S))
+    assert set(bodies) == set(mirrors) and len(mirrors) >= 14
+    got = LK.c_layout(tmp_path, [(cname, [f for f, _ in cls._fields_]) for cname, cls in mirrors.items()])
+    for cname, cls in mirrors.items():
+        fields = [f for f, _ in cls._fields_]
+        declared = [re.sub(r"\[.*", "", f.split("*")[-1].split()[-1]) for d in bodies[cname].split(";") if d.strip() for f in d.split(",")]
+        assert declared == fields, cname
+        assert got[cname]["sizeof"] == C.sizeof(cls), cname
+        for f in fields:
+            assert got[cname][f] == getattr(cls, f).offset, (cname, f)
 
 
 def test_pure_host_helpers_agree_with_spec(built):

@@ -13,39 +13,15 @@ import pytest
 from sorrel_amd import _native as N
 from tests import iqn_forward_common as FC
 from tests.gpu_common import torch_cuda  # noqa: F401
+from tests.learner_common import DEV, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DEV = "cuda:0"
 SETS = FC.load_fixture()
 OUTPUTS = ("qvalues", "quantiles", "taus", "cos")
 # the device library's cosf against float64 cos of the same float32 argument over [0, 64 pi): tools/bench_iqn_forward.py measured at most
 # 1.1852 x 2^-24 over 2^20 taus x 64 frequencies (profiles/iqn_forward.txt); twice that, rounded up to a whole unit of 2^-24
 COS_ULPS = 3
-
-
-class Guarded:
-    """``n`` elements of device memory between two guards of 0xA5 bytes (the body starts as 0xA5 as well); ``shift`` bytes move the
-    body off its 256-byte alignment."""
-
-    def __init__(self, torch, n, np_dtype, shift=0):
-        self.np_dtype = np.dtype(np_dtype)
-        self.total, self.shift = int(n) * self.np_dtype.itemsize, shift
-        self.buf = torch.full((GUARD + shift + self.total + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD + self.shift
-
-    def intact(self):
-        lo = GUARD + self.shift
-        return bool((self.buf[:lo] == 0xA5).all()) and bool((self.buf[lo + self.total:] == 0xA5).all())
-
-    def numpy(self):
-        lo = GUARD + self.shift
-        return self.buf[lo:lo + self.total].cpu().numpy().copy().view(self.np_dtype)
 
 
 def abi_forward(torch, w, states, Nq, *, taus=None, key=None, idx=None, off=(), skip=(), stride=None, untouched=False):

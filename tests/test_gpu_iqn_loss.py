@@ -17,37 +17,13 @@ import pytest
 from sorrel_amd import _native as N
 from tests import iqn_loss_common as LC
 from tests.gpu_common import torch_cuda  # noqa: F401
+from tests.learner_common import DEV, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DEV = "cuda:0"
 SETS = LC.load_fixture()
 INPUTS = ("q_expected", "taus", "q_next_local", "q_next_target", "actions", "rewards", "dones", "valid")
 OUTPUTS = ("grad", "next_actions", "row_terms", "td_error")
-
-
-class Guarded:
-    """``n`` elements of device memory between two guards of 0xA5 bytes (the body starts as 0xA5 as well); ``shift`` bytes move the
-    body off its 256-byte alignment."""
-
-    def __init__(self, torch, n, np_dtype, shift=0):
-        self.np_dtype = np.dtype(np_dtype)
-        self.total, self.shift = int(n) * self.np_dtype.itemsize, shift
-        self.buf = torch.full((GUARD + shift + self.total + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD + self.shift
-
-    def intact(self):
-        lo = GUARD + self.shift
-        return bool((self.buf[:lo] == 0xA5).all()) and bool((self.buf[lo + self.total:] == 0xA5).all())
-
-    def numpy(self):
-        lo = GUARD + self.shift
-        return self.buf[lo:lo + self.total].cpu().numpy().copy().view(self.np_dtype)
 
 
 def abi_loss(torch, qe, taus, ql, qt, actions, rewards, dones, valid, discount, *, off=(), skip=()):

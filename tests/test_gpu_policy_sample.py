@@ -17,32 +17,11 @@ import pytest
 from sorrel_amd import _native as N
 from tests import policy_common as PC
 from tests.gpu_common import torch_cuda  # noqa: F401
+from tests.learner_common import DEV, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DEV = "cuda:0"
 META, SETS = PC.load_fixture()
-
-
-class Guarded:
-    """``nbytes`` of device memory, 8-byte aligned, between two guards of 0xA5 bytes."""
-
-    def __init__(self, torch, n, np_dtype):
-        self.np_dtype = np.dtype(np_dtype)
-        self.total = int(n) * self.np_dtype.itemsize
-        self.buf = torch.full((GUARD + self.total + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 8 == 0
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.total:] == 0xA5).all())
-
-    def numpy(self):
-        return self.buf[GUARD:GUARD + self.total].cpu().numpy().copy().view(self.np_dtype)
 
 
 def abi_sample(torch, x, *, logits=False, stride=None, misalign=False, idx=None, num_envs, agent0=0, seed=0, first_env=0, epoch=0, turn=0,

@@ -18,32 +18,11 @@ import pytest
 from sorrel_amd import _native as N
 from tests import ppo_loss_common as LC
 from tests.gpu_common import torch_cuda  # noqa: F401
+from tests.learner_common import DEV, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DEV = "cuda:0"
 SETS, E2E = LC.load_fixture()
-
-
-class Guarded:
-    """``n`` elements of device memory, 256-byte aligned, between two guards of 0xA5 bytes (the body starts as 0xA5 as well)."""
-
-    def __init__(self, torch, n, np_dtype):
-        self.np_dtype = np.dtype(np_dtype)
-        self.total = int(n) * self.np_dtype.itemsize
-        self.buf = torch.full((GUARD + self.total + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.total:] == 0xA5).all())
-
-    def numpy(self):
-        return self.buf[GUARD:GUARD + self.total].cpu().numpy().copy().view(self.np_dtype)
 
 
 def abi_loss(torch, x, values, actions, old, returns, eps_clip, c, vc=0.5, *, logits=False, stride=None, misalign=False, want_gd=True, want_gv=True,

@@ -12,34 +12,13 @@ import pytest
 from sorrel_amd import _native as N
 from tests import returns_common as RC
 from tests.gpu_common import torch_cuda  # noqa: F401
+from tests.learner_common import DEV, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-DEV = "cuda:0"
 K = RC.chunk()
 FIX = RC.load_fixture()
 MODES = {None: N.RETURNS_NORM_NONE, "column": N.RETURNS_NORM_COLUMN, "all": N.RETURNS_NORM_ALL}
-
-
-class Guarded:
-    """``nbytes`` of device memory, 8-byte aligned, between two guards of 0xA5 bytes."""
-
-    def __init__(self, torch, shape, np_dtype):
-        self.shape, self.np_dtype = tuple(shape), np.dtype(np_dtype)
-        self.total = int(np.prod(shape)) * self.np_dtype.itemsize
-        self.buf = torch.full((GUARD + self.total + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        assert self.buf.data_ptr() % 8 == 0
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + GUARD
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.total:] == 0xA5).all())
-
-    def numpy(self):
-        return self.buf[GUARD:GUARD + self.total].cpu().numpy().copy().view(self.np_dtype).reshape(self.shape)
 
 
 def abi_returns(torch, rewards, dones, *, first, count, capacity, cols, strides, offset=0, gamma, mode=None, f32=False, stats=True):

@@ -11,35 +11,9 @@ from oracle import gridstep_oracle as O
 from sorrel_amd import _native as N
 from tests import sample_common as SC
 from tests.gpu_common import torch_cuda  # noqa: F401
+from tests.learner_common import DEV, Guarded
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 256
-DEV = "cuda:0"
-
-
-class Guarded:
-    """A tensor ``GUARD`` (+ ``offset``) bytes inside a buffer filled with 0xA5."""
-
-    def __init__(self, torch, shape, dtype, offset=0):
-        self.item = torch.empty((), dtype=dtype).element_size()
-        self.total = int(np.prod(shape)) * self.item
-        self.lo = GUARD + offset
-        self.buf = torch.full((self.lo + self.total + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        self.shape, self.dtype = tuple(shape), dtype
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.lo
-
-    def intact(self):
-        return bool((self.buf[:self.lo] == 0xA5).all()) and bool((self.buf[self.lo + self.total:] == 0xA5).all())
-
-    def numpy(self):
-        """(through a host copy of the bytes: the tensor may sit 4 bytes off a 16-byte boundary)"""
-        raw = self.buf[self.lo:self.lo + self.total].cpu().numpy().copy()
-        return raw.view({4: np.float32, 8: np.int64}[self.item]).reshape(self.shape)
-
 
 def abi_sample(torch, states, actions, rewards, dones, n_frames, starts=None, envs=None, *, cols=None, num_starts=None, strides=None,
                offsets=(0, 0), R=None, offset_states=0, seed=0, draw=0, count=None, n=None):
@@ -50,9 +24,9 @@ def abi_sample(torch, states, actions, rewards, dones, n_frames, starts=None, en
     cols = int(states.shape[1]) if cols is None else cols
     R = int(np.prod(states.shape[2:])) if R is None else R
     n = len(starts) if starts is not None else n
-    outs = dict(states=Guarded(torch, (n, n_frames * R), torch.float32, offset_states), next_states=Guarded(torch, (n, n_frames * R), torch.float32),
-                actions=Guarded(torch, (n, 1), torch.int64), rewards=Guarded(torch, (n, 1), torch.float32),
-                dones=Guarded(torch, (n, 1), torch.float32), valid=Guarded(torch, (n, 1), torch.float32), index=Guarded(torch, (n, 2), torch.int64))
+    outs = dict(states=Guarded(torch, (n, n_frames * R), np.float32, offset_states), next_states=Guarded(torch, (n, n_frames * R), np.float32),
+                actions=Guarded(torch, (n, 1), np.int64), rewards=Guarded(torch, (n, 1), np.float32),
+                dones=Guarded(torch, (n, 1), np.float32), valid=Guarded(torch, (n, 1), np.float32), index=Guarded(torch, (n, 2), np.int64))
     d = N.SgwSampleDesc()
     d.states = states.data_ptr() + offsets[0] * states.element_size()
     d.actions = actions.data_ptr() + offsets[1] * actions.element_size()
@@ -349,3 +323,29 @@ def test_buffer_sample_returns_tensors_the_caller_keeps(torch_cuda):
     SC.assert_six(second, SC.np_sample(*host, n_frames, t1, e1), "the second Buffer.sample(5)")
     with pytest.raises(IndexError):
         buf.sample(2, starts=[0, cap - n_frames + 1], envs=[0, 0])
+
+
+# ------------------------------------------------------------------------------------------------------------- a ring on another device
+def test_a_ring_on_a_device_that_is_not_the_current_one(torch_cuda):
+    """``TurnBuffer.sample`` and ``returns()`` of a ring on ``cuda:1`` while ``cuda:0`` is current: the launch is made under the ring's
+    device (its pointers and its stream belong there), the results are the host expectations, and the current device stays 0."""
+    torch = torch_cuda
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    from sorrel_amd.buffers import _returns_torch
+    from tests import returns_common as RC
+
+    torch.cuda.set_device(0)
+    ring, host = SC.turn_ring(torch, "cuda:1", torch.float32)
+    cap, E, A = host[1].shape
+    starts, envs = SC.turn_indices(cap, E * A, 1)
+    got = ring.sample(len(starts), starts=starts, envs=envs)
+    assert all(t.device == ring.device for t in got)
+    SC.assert_six(got, SC.turn_expected(host, None, 1, starts, envs), "TurnBuffer.sample on cuda:1 under cuda:0")
+    res = ring.returns(0.9, normalize="column")
+    raw = _returns_torch(torch.from_numpy(host[2]), torch.from_numpy(host[3]), 0.9, 0, cap).returns.numpy()
+    assert np.array_equal(res.returns.cpu().numpy(), raw)
+    flat = raw.reshape(cap, E * A)
+    RC.assert_normalized(res.normalized.cpu().numpy().reshape(cap, E * A), RC.host_normalized(flat, "column")[0], RC.tolerance(flat, axis=0),
+                         "returns() on cuda:1 under cuda:0")
+    assert torch.cuda.current_device() == 0

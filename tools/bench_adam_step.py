@@ -18,13 +18,13 @@ hold the real formulas).  Algorithmic bytes of the third shape: ``4 N`` read for
 the update."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from _timing import Emitter, one, stats  # noqa: E402  (tools/_timing.py)
 
 from sorrel_amd import optim  # noqa: E402
 
@@ -37,20 +37,6 @@ def iqn_shapes(inputs=6 * 5 * 5, frames=5, units=250, actions=4, n_cos=64):
 def actor_critic_shapes(inputs=6 * 5 * 5, units=64, actions=4):
     net = lambda out: [(units, inputs), (units,), (2 * units, units), (2 * units,), (units, 2 * units), (units,), (out, units), (out,)]  # noqa: E731
     return net(actions), net(1)
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 class Case:
@@ -106,11 +92,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_adam_step needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
+    emit = Emitter(args.out)
 
     dev = torch.device("cuda:0")
     emit(f"# tools/bench_adam_step.py --reps {args.reps}: {torch.cuda.get_device_name(0)}; microseconds per call, device events around each call, "
@@ -163,10 +145,7 @@ def main():
         emit(line)
         del case
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    emit.close()
 
 
 if __name__ == "__main__":

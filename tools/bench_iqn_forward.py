@@ -17,44 +17,18 @@ agree to 1e-4 of the largest magnitude and the greedy actions are counted).  FLO
 achieved rate is set against the chip's 155 TFLOP/s of float32-input matrix instructions."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from _timing import Emitter, series, stats  # noqa: E402  (tools/_timing.py)
 
 from sorrel_amd.models import iqn as M  # noqa: E402
 
 PEAK_TF = 155.0
 SHAPES = tuple((n, 875, 250, 12, 4) for n in (1024, 16384, 65536)) + tuple((n, 875, 64, 8, 4) for n in (1024, 16384, 65536))
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def series(fns, reps, warm=3):
-    for _ in range(warm):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(reps):
-        for f, o in zip(fns, out):
-            o.append(one(f))
-    return out
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 def cos_sweep(dev, emit):
@@ -82,11 +56,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_iqn_forward needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
+    emit = Emitter(args.out)
 
     dev = torch.device("cuda:0")
     emit(f"# tools/bench_iqn_forward.py --reps {args.reps}: {torch.cuda.get_device_name(0)}; float32 states and weights, eval mode; microseconds per call, "
@@ -119,7 +89,7 @@ def main():
         del quant
         if not worst <= 1e-4:
             raise SystemExit(f"n={n} L={L} N={Nq}: sgw_iqn_forward differs from the torch path by {worst:.3e} of the largest magnitude")
-        t_a, t_k, t_b = series((by_torch, kernel, by_torch), args.reps)
+        t_a, t_k, t_b = series((by_torch, kernel, by_torch), args.reps, warm=3)
         (ma, la, ha), (mb, lb, hb), (mk, lk, hk) = stats(t_a), stats(t_b), stats(t_k)
         base, spread = (ma + mb) / 2, abs(ma - mb)
         flop = 2.0 * n * (D * L + Nq * (64 * L + L * L + L * (A + 1)))
@@ -131,10 +101,7 @@ def main():
              f"{flop / mk / 1e6:.2f} TFLOP/s over the call's time ({100 * flop / mk / 1e6 / PEAK_TF:.1f} % of {PEAK_TF:.0f}); torch {flop / base / 1e6:.2f} TFLOP/s")
         del net, x, taus, res
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    emit.close()
 
 
 if __name__ == "__main__":

@@ -17,44 +17,18 @@ actions must be equal, the gradient within ``N 2^-23`` of its largest magnitude 
 bytes: ``16 B N A`` -- three float32 ``[B, N, A]`` tensors read and one written."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from _timing import Emitter, series, stats  # noqa: E402  (tools/_timing.py)
 
 from sorrel_amd import losses  # noqa: E402
 
 DISCOUNT = 0.99 ** 3
 SHAPES = tuple((B, N, A) for B in (64, 1024, 65536) for N in (12, 32) for A in (4, 8, 16))
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def series(fns, reps, warm=3):
-    for _ in range(warm):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(reps):
-        for f, o in zip(fns, out):
-            o.append(one(f))
-    return out
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 def batch(B, N, A, dev):
@@ -75,11 +49,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_iqn_loss needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
+    emit = Emitter(args.out)
 
     dev = torch.device("cuda:0")
     emit(f"# tools/bench_iqn_loss.py --reps {args.reps}: {torch.cuda.get_device_name(0)}; discount {DISCOUNT:.6f}; float32 quantiles, float64 valid; "
@@ -107,7 +77,7 @@ def main():
         worst_l = float((res.loss - L).abs() / L.abs())
         if not (worst_g <= N * 2.0 ** -23 and worst_l <= 2.0 ** -40):
             raise SystemExit(f"B={B} N={N} A={A}: sgw_iqn_loss differs from the torch path: gradient {worst_g:.3e} of the largest magnitude, loss {worst_l:.3e}")
-        t_a, t_k, t_b = series((by_torch, kernel, by_torch), args.reps)
+        t_a, t_k, t_b = series((by_torch, kernel, by_torch), args.reps, warm=3)
         (ma, la, ha), (mb, lb, hb), (mk, lk, hk) = stats(t_a), stats(t_b), stats(t_k)
         base, spread = (ma + mb) / 2, abs(ma - mb)
         moved = 16 * B * N * A
@@ -118,10 +88,7 @@ def main():
              f"than the spread; {moved / 1e6:.3f} MB algorithmic -> {moved / mk / 1e6:.4f} TB/s over the call's time (HBM peak 8 TB/s)")
         del qe, taus, ql, qt, actions, rewards, dones, valid, res, leaf, L, _td, a_star, _ql
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    emit.close()
 
 
 if __name__ == "__main__":

@@ -26,39 +26,14 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from _timing import Emitter, series, stats  # noqa: E402  (tools/_timing.py)
 from torch.distributions import Categorical  # noqa: E402
 
 from sorrel_amd import _native as N  # noqa: E402
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def series(fns, reps, warm=5):
-    for _ in range(warm):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(reps):
-        for f, o in zip(fns, out):
-            o.append(one(f))
-    return out
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 def ulps(a, b):
@@ -112,7 +87,7 @@ def launch_case(E, na, reps, emit):
     if u_lp > 1 or u_en > 1:
         raise SystemExit(f"E={E} n_actions={na}: log-probabilities {u_lp} ulp, entropies {u_en} ulp from Categorical in float64")
     verdict = f"counts within {dev_sd:.2f} sd; log-prob {u_lp} ulp, entropy {u_en} ulp from float64 Categorical"
-    t_a, t_k, t_b = series((by_torch, kernel, by_torch), reps)
+    t_a, t_k, t_b = series((by_torch, kernel, by_torch), reps, warm=5)
     (ma, la, ha), (mb, lb, hb), (mk, lk, hk) = stats(t_a), stats(t_b), stats(t_k)
     base, spread = (ma + mb) / 2, abs(ma - mb)
     moved = E * (4 * na + 16)
@@ -207,15 +182,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_policy_sample needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
-        if args.out:                          # (kept as it grows: a later case that fails leaves the earlier lines)
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "w") as fh:
-                fh.write("\n".join(lines) + "\n")
+    emit = Emitter(args.out, as_it_grows=True)          # (kept as it grows: a later case that fails leaves the earlier lines)
 
     emit(f"# tools/bench_policy_sample.py --reps {args.reps} --envs {' '.join(map(str, args.envs))} --turns {args.turns} --rounds {args.rounds}: "
          f"{torch.cuda.get_device_name(0)}; launches: microseconds per call, device events around each call, paths alternating call by call "

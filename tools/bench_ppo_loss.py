@@ -19,45 +19,19 @@ autograd adds: a clone of the scalar, the multiply of either saved gradient by t
 8 + 8 + 8 + 4 read for value, action, return and stored log-probability, 8 written for the value's gradient."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from _timing import Emitter, series, stats  # noqa: E402  (tools/_timing.py)
 
 from sorrel_amd import losses  # noqa: E402
 from sorrel_amd.models import ActionProbs  # noqa: E402
 
 EPS_CLIP, ENTROPY_COEF = 0.2, 0.01
 SHAPES = ((100 * 65536, 4), (100 * 65536, 16), (100 * 1024, 4), (100 * 1024, 16), (65536, 256))
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def series(fns, reps, warm=3):
-    for _ in range(warm):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(reps):
-        for f, o in zip(fns, out):
-            o.append(one(f))
-    return out
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 def batch(n, na, dev):
@@ -78,11 +52,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_ppo_loss needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
+    emit = Emitter(args.out)
 
     dev = torch.device("cuda:0")
     emit(f"# tools/bench_ppo_loss.py --reps {args.reps}: {torch.cuda.get_device_name(0)}; eps_clip {EPS_CLIP}, entropy_coef {ENTROPY_COEF}; float64; "
@@ -118,7 +88,7 @@ def main():
         torch.cuda.synchronize()
         if not (torch.equal(kp.grad, res.grad_dist) and torch.equal(kv.grad, res.grad_values)):
             raise SystemExit(f"n={n} A={na}: ppo_loss(...).backward() differs from ppo_loss_terms")
-        t_a, t_k, t_w, t_b = series((by_torch, kernel, wrapper, by_torch), args.reps)
+        t_a, t_k, t_w, t_b = series((by_torch, kernel, wrapper, by_torch), args.reps, warm=3)
         (ma, la, ha), (mb, lb, hb), (mk, lk, hk), (mw, lw, hw) = stats(t_a), stats(t_b), stats(t_k), stats(t_w)
         base, spread = (ma + mb) / 2, abs(ma - mb)
         moved = n * (16 * na + 36)
@@ -130,10 +100,7 @@ def main():
         emit(f"{'':22s} ppo_loss().backward() {mw:10.1f} us (p10 {lw:.1f}, p90 {hw:.1f}): autograd's clone, multiplies and accumulation add {mw - mk:.1f} us")
         del probs, values, actions, old, returns, res, lp, lv, kp, kv, L
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    emit.close()
 
 
 if __name__ == "__main__":

@@ -16,43 +16,17 @@ of the tests, ``8 T 2^-53 (1 + max|x| / (std + 1e-7))``.  Algorithmic bytes per 
 normalisation."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from _timing import Emitter, series, stats  # noqa: E402  (tools/_timing.py)
 
 from sorrel_amd.buffers import Buffer, TurnBuffer, _returns_torch, _returns_views  # noqa: E402
 
 GAMMA = 0.99
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def series(fns, reps, warm=3):
-    for _ in range(warm):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(reps):
-        for f, o in zip(fns, out):
-            o.append(one(f))
-    return out
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 def fill(ring):
@@ -89,11 +63,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_returns needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
+    emit = Emitter(args.out)
 
     dev, T, A = "cuda:0", args.turns, args.agents
     emit(f"# tools/bench_returns.py --reps {args.reps} --turns {T} --agents {A} --envs {' '.join(map(str, args.envs))}: {torch.cuda.get_device_name(0)}; "
@@ -117,7 +87,7 @@ def main():
             verdict = compare(name, got, want, mode)
             kernel = lambda: ring.returns(GAMMA, normalize=mode, out=got, **kw)                      # noqa: E731
             by_torch = lambda: _returns_torch(rewards, dones, GAMMA, 0, T, normalize=mode, out=want)   # noqa: E731
-            t_a, t_k, t_b = series((by_torch, kernel, by_torch), args.reps)
+            t_a, t_k, t_b = series((by_torch, kernel, by_torch), args.reps, warm=3)
             (ma, la, ha), (mb, lb, hb), (mk, lk, hk) = stats(t_a), stats(t_b), stats(t_k)
             base, spread = (ma + mb) / 2, abs(ma - mb)
             moved = T * cols * (12 if mode is None else 24)
@@ -127,10 +97,7 @@ def main():
             del got, want
         del ring, rewards, dones
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    emit.close()
 
 
 if __name__ == "__main__":

@@ -18,42 +18,16 @@ the timed, seeded indices (the device-drawn batch against the torch path at ``la
 (n_frames + 1) rows read + 2 n_frames rows written (+ the scalars)."""
 import argparse
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from _timing import Emitter, series, stats  # noqa: E402  (tools/_timing.py)
 
 from sorrel_amd.buffers import Buffer, ReplaySampler, TurnBuffer, _stack_torch  # noqa: E402
 from sorrel_amd.spec import treasurehunt_spec  # noqa: E402
-
-
-def one(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3          # microseconds
-
-
-def series(fns, reps, warm=10):
-    for _ in range(warm):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(reps):
-        for f, o in zip(fns, out):
-            o.append(one(f))
-    return out
-
-
-def stats(xs):
-    xs = sorted(xs)
-    return statistics.median(xs), xs[len(xs) // 10], xs[(9 * len(xs)) // 10]
 
 
 def same(a, b):
@@ -61,7 +35,7 @@ def same(a, b):
 
 
 def report(emit, name, B, F, R, src_bytes, paths, reps):
-    t_a, t_host, t_b, t_dev = series(paths, reps)
+    t_a, t_host, t_b, t_dev = series(paths, reps, warm=10)
     (ma, la, ha), (mb, lb, hb) = stats(t_a), stats(t_b)
     (mh, lh, hh), (md, ld, hd) = stats(t_host), stats(t_dev)
     base, spread = (ma + mb) / 2, abs(ma - mb)
@@ -83,11 +57,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sample needs a HIP device")
-    lines = []
-
-    def emit(text):
-        print(text, flush=True)
-        lines.append(text)
+    emit = Emitter(args.out)
 
     dev = "cuda:0"
     window = tuple(treasurehunt_spec(32, 32, 8, 3).obs_shape[1:])
@@ -150,10 +120,7 @@ def main():
         report(emit, "TurnBuf u8", B, F, R, 1, (by_hand, lambda: ring.sample(B, agent=3, n_frames=F, starts=t0, envs=e), by_hand, sampler.sample), args.reps)
         del ring, sampler
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    emit.close()
 
 
 if __name__ == "__main__":
