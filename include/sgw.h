@@ -1031,6 +1031,76 @@ int64_t sgw_iqn_forward_workspace_bytes(int64_t n, int32_t layer_size);
  * recordable. */
 int sgw_turn_iqn_forward(sgw_engine* eng, int32_t agent, const sgw_iqn_forward_desc* desc, void* stream);
 
+/* ---- IQN's network backward (what torch's autograd runs behind sorrel/models/pytorch/iqn.py:322-412's loss.backward(): from
+ * dL/dquantiles to the gradients of the ten effective weights, in two launches) ----
+ * Reads everything sgw_iqn_forward reads, with the same types, strides and limits (states with state_type and state_stride, the ten
+ * effective weights, n, in_features = D, layer_size = L 1..256, num_quantiles = N 1..64, num_actions = A 1..64, n_cos = 64), and
+ *   taus            float32 [n][N], required: the backward never draws taus;
+ *   h               float32 [n][L]: the forward's workspace after the call whose gradient this is;
+ *   grad_quantiles  float32 [n][N][A], dense: it need not be one-hot in a.
+ * All arithmetic is float32.  Every dot product and every reduction below is ONE fmaf chain in ascending index order that starts at +0
+ * (the forward's own chains start at the bias, as before): chain_i(a_i, b_i) = fmaf(a_I-1, b_I-1, ... fmaf(a_0, b_0, +0)).  c, e, z
+ * and y are recomputed exactly as sgw_iqn_forward defines them, with the same bits.  mask(x) = !(x <= 0): torch's threshold_backward, 0
+ * at 0, and a NaN passes the gradient; it is taken from the stored post-activation value (y <= 0 iff y_pre <= 0, because relu maps those
+ * to +0).  With m = a quantile row (m = s N + q), s(m) = its state and g = grad_quantiles[m]:
+ *   dueling   G = ((g_0 + g_1) + ...), summed serially;  dval = G;  dadv_a = g_a - G / (float)A;  dO[m] = (dadv_0 .. dadv_(A-1), dval)
+ *   dy_j      = mask(y_j) ? chain_o(dO_o, Wo[o][j]), o = 0..A : +0, where Wo = w_adv's rows followed by w_val
+ *   dz_k      = chain_j(dy_j, w_ff[j][k])
+ *   de_k      = mask(e_k) ? dz_k * h[s][k] : +0
+ *   dh[s][k]  = (((dz_k e_k)_q=0 + (dz_k e_k)_q=1) + ...), summed serially over the state's quantiles, every product rounded first
+ *   dhp       = mask(h) ? dh : +0
+ * Every weight gradient is a chain over the batch rows, ascending (on __builtin_amdgcn_mfma_f32_32x32x2f32 with the batch row as its k:
+ * the k-ordered fmaf chain that starts at C, as in the forward):
+ *   out_w_adv[o][k] = chain_m(dO[m][o], y[m][k]), o < A;   out_w_val[k] = chain_m(dO[m][A], y[m][k])
+ *   out_w_ff[j][k]  = chain_m(dy[m][j], z[m][k])
+ *   out_w_cos[j][i] = chain_m(de[m][j], c[m][i])
+ *   out_w_head[j][d] = chain_s(dhp[s][j], (float)state[s][d])
+ * and every bias gradient the same chain with the activation replaced by 1.  Nothing flows to the states or to the taus.
+ * Outputs: ten pointers, one per effective weight and in its shape, each optional (NULL); out_grad_h [n][L] = dh, optional.
+ * workspace: sgw_iqn_backward_workspace_bytes(...) bytes, 4-byte aligned, overwritten: z, y, dy, de [n N][L], c [n N][64],
+ * dO [n N][A + 1] and dhp [n][L] pass through memory between the two launches ON PURPOSE: a learner's batch is a sampled batch (64
+ * states in the reference), and the forward's rule that nothing of size n N L reaches memory was written for acting.  The weight
+ * gradients are serial in the batch rows: one wave owns each 32 x 32 tile of a gradient for all rows.  No float atomics: two calls give
+ * the same bits.  Non-finite inputs give what IEEE arithmetic gives.  Needs no engine; all pointers are device pointers.  Asynchronous
+ * on `stream`; a NULL required pointer (states, a weight, taus, h, grad_quantiles), a misaligned pointer, sizes out of range (as
+ * sgw_iqn_forward's), a missing or short workspace, a non-zero reserved field and offsets beyond 64 bits are SGW_EINVAL with the reason
+ * in sgw_last_error(), before anything is launched.  n == 0 launches nothing and writes nothing. */
+typedef struct sgw_iqn_backward_desc {
+    const void* states;          /* [n] rows of in_features elements of state_type, state_stride elements apart */
+    const float* w_head;         /* the ten effective weights, as in sgw_iqn_forward_desc */
+    const float* b_head;
+    const float* w_cos;
+    const float* b_cos;
+    const float* w_ff;
+    const float* b_ff;
+    const float* w_adv;
+    const float* b_adv;
+    const float* w_val;
+    const float* b_val;
+    const float* taus;           /* [n][N] */
+    const float* h;              /* [n][L] */
+    const float* grad_quantiles; /* [n][N][A] */
+    float* out_w_head;           /* [L][D], or NULL; and so on: each in its weight's shape */
+    float* out_b_head;
+    float* out_w_cos;
+    float* out_b_cos;
+    float* out_w_ff;
+    float* out_b_ff;
+    float* out_w_adv;
+    float* out_b_adv;
+    float* out_w_val;
+    float* out_b_val;
+    float* out_grad_h;           /* [n][L], or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t n, state_stride;
+    int32_t in_features, layer_size, num_quantiles, num_actions, n_cos, state_type;
+    int32_t reserved0, reserved1;    /* reserved: 0 */
+} sgw_iqn_backward_desc;
+int sgw_iqn_backward(const sgw_iqn_backward_desc* desc, void* stream);
+/* Bytes of workspace a call needs (0 for no rows); a negative code for n outside [0, 2^40) or a size outside sgw_iqn_backward's ranges. */
+int64_t sgw_iqn_backward_workspace_bytes(int64_t n, int32_t in_features, int32_t layer_size, int32_t num_quantiles, int32_t num_actions);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

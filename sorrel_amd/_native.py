@@ -235,6 +235,26 @@ class SgwIqnForwardDesc(C.Structure):
     ]
 
 
+class SgwIqnBackwardDesc(C.Structure):
+    """Mirror of ``struct sgw_iqn_backward_desc`` (include/sgw.h): one ``sgw_iqn_backward`` call."""
+
+    _fields_ = [
+        ("states", C.c_void_p),
+        ("w_head", C.c_void_p), ("b_head", C.c_void_p), ("w_cos", C.c_void_p), ("b_cos", C.c_void_p), ("w_ff", C.c_void_p), ("b_ff", C.c_void_p),
+        ("w_adv", C.c_void_p), ("b_adv", C.c_void_p), ("w_val", C.c_void_p), ("b_val", C.c_void_p),
+        ("taus", C.c_void_p), ("h", C.c_void_p), ("grad_quantiles", C.c_void_p),
+        ("out_w_head", C.c_void_p), ("out_b_head", C.c_void_p), ("out_w_cos", C.c_void_p), ("out_b_cos", C.c_void_p), ("out_w_ff", C.c_void_p),
+        ("out_b_ff", C.c_void_p), ("out_w_adv", C.c_void_p), ("out_b_adv", C.c_void_p), ("out_w_val", C.c_void_p), ("out_b_val", C.c_void_p),
+        ("out_grad_h", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_int64),
+        ("n", C.c_int64), ("state_stride", C.c_int64),
+        ("in_features", C.c_int32), ("layer_size", C.c_int32), ("num_quantiles", C.c_int32), ("num_actions", C.c_int32), ("n_cos", C.c_int32),
+        ("state_type", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 class SgwAdamTensor(C.Structure):
     """Mirror of ``struct sgw_adam_tensor`` (include/sgw.h): one tensor of an ``sgw_adam_plan`` call."""
 
@@ -345,6 +365,8 @@ PROTOTYPES = {
     "sgw_iqn_forward": (_rc, [C.POINTER(SgwIqnForwardDesc), _vp]),
     "sgw_iqn_forward_workspace_bytes": (_i64, [_i64, _i32]),
     "sgw_turn_iqn_forward": (_rc, [_vp, _i32, C.POINTER(SgwIqnForwardDesc), _vp]),
+    "sgw_iqn_backward": (_rc, [C.POINTER(SgwIqnBackwardDesc), _vp]),
+    "sgw_iqn_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
     "sgw_adam_plan_bytes": (_i64, [_i64, _i64]),
     "sgw_adam_plan": (_rc, [C.POINTER(SgwAdamTensor), _i64, _i32, _vp, _i64, C.POINTER(SgwAdamPlanInfo)]),
     "sgw_adam_step": (_rc, [C.POINTER(SgwAdamStepDesc), _vp]),

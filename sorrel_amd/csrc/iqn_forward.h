@@ -54,7 +54,8 @@ __device__ __forceinline__ float fwd_relu(const float x) { return x > 0.0f ? x :
 // acc[rt] += A[64][K] x W[rows][K]^T for the calling wave's column tile w, rt = the 32-row tile.
 // HEAD: A's k-tile is staged from the states (row0 .. row0 + mrows) into As beside the weights; else A is an LDS image of stride `as`
 // that holds every k < ceil32(K).  Ends with a barrier: the caller may overwrite A and Wl.
-template <bool HEAD, bool U8>
+// TRANS: W is [K][rows] (the product with a weight's transpose: the backward's dz); its tile is staged with loads that run along the rows.
+template <bool HEAD, bool U8, bool TRANS = false>
 __device__ __forceinline__ void fwd_gemm(fwd_f16 (&acc)[2], const float* A, const int as, float* As, const IqnFwdParams& p, const int64_t row0,
                                          const int mrows, const float* __restrict__ W, const int rows, const int K, float* Wl, const int CT, const bool two) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 31, lk = lane >> 5;
@@ -68,8 +69,13 @@ __device__ __forceinline__ void fwd_gemm(fwd_f16 (&acc)[2], const float* A, cons
         const int k = k0 + kq, kc = k < kmax ? k : kmax;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int j = j0 + 16 * i, jc = j < jmax ? j : jmax;
-            wreg[i] = W[(int64_t)jc * K + kc];
+            if constexpr (TRANS) {
+                const int j = kq + 32 * (i & 7), jc = j < jmax ? j : jmax, kt = k0 + j0 + 16 * (i >> 3), ktc = kt < kmax ? kt : kmax;
+                wreg[i] = W[(int64_t)ktc * rows + jc];
+            } else {
+                const int j = j0 + 16 * i, jc = j < jmax ? j : jmax;
+                wreg[i] = W[(int64_t)jc * K + kc];
+            }
         }
         if constexpr (HEAD) {
 #pragma unroll
@@ -86,7 +92,14 @@ __device__ __forceinline__ void fwd_gemm(fwd_f16 (&acc)[2], const float* A, cons
         const bool kin = k0 + kq < K;
         __syncthreads();                      // the products of the previous k-tile have read Wl (and As)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) Wl[(j0 + 16 * i) * kFwdWS + kq] = (kin && j0 + 16 * i < rows) ? wreg[i] : -0.0f;
+        for (int i = 0; i < 16; ++i) {
+            if constexpr (TRANS) {
+                const int j = kq + 32 * (i & 7), kt = j0 + 16 * (i >> 3);
+                Wl[j * kFwdWS + kt] = (k0 + kt < K && j < rows) ? wreg[i] : -0.0f;
+            } else {
+                Wl[(j0 + 16 * i) * kFwdWS + kq] = (kin && j0 + 16 * i < rows) ? wreg[i] : -0.0f;
+            }
+        }
         if constexpr (HEAD) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) As[(j0 + 16 * i) * kFwdWS + kq] = (kin && j0 + 16 * i < mrows) ? areg[i] : 0.0f;

@@ -79,6 +79,7 @@ namespace {
 #include "iqn_loss.h"
 #include "adam_step.h"
 #include "iqn_forward.h"
+#include "iqn_backward.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -1612,6 +1613,90 @@ int sgw_turn_iqn_forward(sgw_engine* e, int32_t agent, const sgw_iqn_forward_des
     sgw_iqn_forward_desc d = *desc;
     d.num_envs = e->cfg.num_envs; d.seed = e->cfg.seed; d.first_env = e->cfg.first_env_id; d.agent0 = agent; d.epoch = 0; d.turn = 0;
     return iqn_forward_launch(&d, e->d_turn, "sgw_turn_iqn_forward", stream);
+}
+
+// ---------------------------------------------------------------- IQN's network backward (iqn_backward.h)
+// floats of workspace per quantile row (z, y, dy, de, c, dO) and per state (dhp)
+static int64_t iqn_backward_floats(int64_t n, int64_t L, int64_t N, int64_t A) { return n * N * (4 * L + SGW_IQN_N_COS + A + 1) + n * L; }
+
+static int iqn_backward_sizes(const char* who, int64_t n, int32_t D, int32_t L, int32_t N, int32_t A) {
+    if (n < 0 || n >= ((int64_t)1 << 40)) return fail(SGW_EINVAL, "%s: n = %lld outside [0, 2^40)", who, (long long)n);
+    if (D < 1) return fail(SGW_EINVAL, "%s: in_features = %d", who, D);
+    if (L < 1 || L > kFwdMaxL) return fail(SGW_EINVAL, "%s: layer_size = %d outside [1, %d]", who, L, kFwdMaxL);
+    if (N < 1 || N > kFwdM) return fail(SGW_EINVAL, "%s: num_quantiles = %d outside [1, %d]", who, N, kFwdM);
+    if (A < 1 || A > SGW_IQN_MAX_ACTIONS) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, A, SGW_IQN_MAX_ACTIONS);
+    return SGW_OK;
+}
+
+int64_t sgw_iqn_backward_workspace_bytes(int64_t n, int32_t in_features, int32_t layer_size, int32_t num_quantiles, int32_t num_actions) {
+    if (int rc = iqn_backward_sizes("sgw_iqn_backward_workspace_bytes", n, in_features, layer_size, num_quantiles, num_actions)) return rc;
+    return iqn_backward_floats(n, layer_size, num_quantiles, num_actions) * (int64_t)sizeof(float);     // (< 2^40 * 2^17 * 4)
+}
+
+int sgw_iqn_backward(const sgw_iqn_backward_desc* d, void* stream) {
+    const char* who = "sgw_iqn_backward";
+    if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
+    if (!d->states || !d->w_head || !d->b_head || !d->w_cos || !d->b_cos || !d->w_ff || !d->b_ff || !d->w_adv || !d->b_adv || !d->w_val || !d->b_val)
+        return fail(SGW_EINVAL, "%s: states and the ten weight pointers must not be NULL", who);
+    if (!d->taus || !d->h || !d->grad_quantiles) return fail(SGW_EINVAL, "%s: taus, h and grad_quantiles must not be NULL", who);
+    if (int rc = iqn_backward_sizes(who, d->n, d->in_features, d->layer_size, d->num_quantiles, d->num_actions)) return rc;
+    if (d->n_cos != SGW_IQN_N_COS) return fail(SGW_EINVAL, "%s: n_cos = %d: only %d is built", who, d->n_cos, SGW_IQN_N_COS);
+    if (d->state_type != SGW_IQN_STATE_F32 && d->state_type != SGW_IQN_STATE_U8) return fail(SGW_EINVAL, "%s: unknown state_type %d", who, d->state_type);
+    if (d->state_stride < d->in_features) return fail(SGW_EINVAL, "%s: state_stride = %lld is smaller than in_features = %d", who, (long long)d->state_stride, d->in_features);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
+    if (d->state_type == SGW_IQN_STATE_F32 && misaligned(3, {d->states})) return fail(SGW_EINVAL, "%s: states is not aligned to its element type", who);
+    if (misaligned(3, {d->w_head, d->b_head, d->w_cos, d->b_cos, d->w_ff, d->b_ff, d->w_adv, d->b_adv, d->w_val, d->b_val, d->taus, d->h, d->grad_quantiles,
+                       d->out_w_head, d->out_b_head, d->out_w_cos, d->out_b_cos, d->out_w_ff, d->out_b_ff, d->out_w_adv, d->out_b_adv, d->out_w_val,
+                       d->out_b_val, d->out_grad_h, d->workspace}))
+        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (a weight, taus, h, grad_quantiles, an output or the workspace)", who);
+    // the largest byte offsets: 4 n state_stride (states); the workspace's (n < 2^40: below 2^59)
+    if (d->n > INT64_MAX / 8 / d->state_stride)
+        return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->state_stride);
+    const int64_t n = d->n, L = d->layer_size, N = d->num_quantiles, A = d->num_actions, D = d->in_features, M = n * N;
+    if (int rc = workspace_short(who, d->workspace, d->workspace_bytes, iqn_backward_floats(n, L, N, A) * (int64_t)sizeof(float))) return rc;
+    if (n == 0) return SGW_OK;
+    IqnBwdParams b{};
+    IqnFwdParams& p = b.f;
+    p.states = d->states;
+    p.w_head = d->w_head; p.b_head = d->b_head; p.w_cos = d->w_cos; p.b_cos = d->b_cos; p.w_ff = d->w_ff; p.b_ff = d->b_ff;
+    p.w_adv = d->w_adv; p.b_adv = d->b_adv; p.w_val = d->w_val; p.b_val = d->b_val; p.taus = d->taus;
+    p.h = const_cast<float*>(d->h);           // (read only here)
+    p.n = n; p.stride = d->state_stride; p.num_envs = 1;
+    p.D = (int32_t)D; p.L = (int32_t)L; p.N = (int32_t)N; p.A = (int32_t)A; p.u8 = d->state_type == SGW_IQN_STATE_U8;
+    p.R = kFwdM / (int32_t)N;
+    p.q_tiles = ceil_div(n, p.R);
+    b.grad = d->grad_quantiles;
+    float* w = static_cast<float*>(d->workspace);
+    b.z = w; b.y = b.z + M * L; b.dy = b.y + M * L; b.de = b.dy + M * L; b.c = b.de + M * L; b.dO = b.c + M * SGW_IQN_N_COS; b.dhp = b.dO + M * (A + 1);
+    b.out_dh = d->out_grad_h;
+    IqnWgradParams g{};
+    int32_t tiles = 0;
+    auto job = [&](int i, const float* G, int64_t gs, int64_t J, const void* act, int64_t as, int64_t K, int64_t rows, bool u8, float* out_w, float* out_b) {
+        IqnWgradJob& jb = g.job[i];
+        jb.G = G; jb.act = act; jb.out_w = out_w; jb.out_b = out_b;
+        jb.M = rows; jb.gs = gs; jb.as = as;
+        jb.J = (int32_t)J; jb.K = (int32_t)K; jb.u8 = u8;
+        // the column tiles that hold something asked for: all of [0, K) for the weight, the one of column K for the bias
+        const int32_t last = (int32_t)(K / 32);
+        jb.kt0 = out_w ? 0 : last;
+        jb.kts = out_w ? (out_b ? last + 1 : (int32_t)ceil_div(K, 32)) : (out_b ? 1 : 0);
+        jb.tile0 = tiles;
+        tiles += jb.kts * (int32_t)ceil_div(J, 32);
+    };
+    job(0, b.dO, A + 1, A, b.y, L, L, M, false, d->out_w_adv, d->out_b_adv);
+    job(1, b.dO + A, A + 1, 1, b.y, L, L, M, false, d->out_w_val, d->out_b_val);
+    job(2, b.dy, L, L, b.z, L, L, M, false, d->out_w_ff, d->out_b_ff);
+    job(3, b.de, L, L, b.c, SGW_IQN_N_COS, SGW_IQN_N_COS, M, false, d->out_w_cos, d->out_b_cos);
+    job(4, b.dhp, L, L, d->states, d->state_stride, D, n, p.u8 != 0, d->out_w_head, d->out_b_head);
+    g.tiles = tiles;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(iqn_bwd_rows_kernel, dim3((unsigned)std::min<int64_t>(p.q_tiles, kFwdMaxBlocks)), dim3(kFwdThreads), 0, s, b);
+    HIP_TRY(hipGetLastError());
+    if (tiles > 0) {
+        hipLaunchKernelGGL(iqn_wgrad_kernel, dim3((unsigned)ceil_div(tiles, kBwdWaves)), dim3(64 * kBwdWaves), 0, s, g);
+        HIP_TRY(hipGetLastError());
+    }
+    return SGW_OK;
 }
 
 // ---------------------------------------------------------------- Adam, clipping and the soft update (adam_step.h)

@@ -23,6 +23,13 @@ outputs and ``loss.backward()``) has the same three forms -- ``iqn_loss_terms`` 
     loss = iqn_loss(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, GAMMA ** n_step)
     optimizer.zero_grad(); loss.backward(); clip_grad_norm_(local.parameters(), 1); optimizer.step()
     # or, with optimizer = sorrel_amd.optim.FusedAdam(local.parameters(), max_grad_norm=1, target_params=target.parameters(), tau=TAU): optimizer.step() alone
+
+With ``sorrel_amd.models.iqn.IQN`` the three network calls run without torch's network ops as well (``sgw_iqn_forward``, and
+``sgw_iqn_backward`` behind ``loss.backward()``)::
+
+    q_next_local = local.quantiles(next_states).quantiles; q_next_target = target.quantiles(next_states).quantiles
+    q_expected, taus = local.forward_fused(states)
+    loss = iqn_loss(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, GAMMA ** n_step); loss.backward(); optimizer.step()
 """
 from __future__ import annotations
 

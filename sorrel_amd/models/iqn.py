@@ -5,6 +5,8 @@ parameter and buffer names and shapes so that its ``state_dict`` loads, and the 
 * ``IQN.quantiles`` / ``IQN.get_qvalues`` run ``sgw_iqn_forward`` (``sorrel_amd/csrc/iqn_forward.h``: two launches, nothing of size
   ``[B N, L]`` through memory) for device tensors, without autograd: acting, and the two ``next_states`` calls of a learner's step.  The
   taus are given, or drawn KEYED by (seed, env, epoch, turn, agent, quantile) so that a recorded turn draws fresh ones on every replay.
+* ``IQN.forward_fused`` gives ``forward``'s results with autograd on the device: ``sgw_iqn_forward`` forwards, one ``sgw_iqn_backward``
+  call (``sorrel_amd/csrc/iqn_backward.h``) backwards: the ``q_expected`` call of a learner's step.
 * ``IQNActor`` is a ``BaseModel`` around an ``IQN`` whose ``take_action`` returns the float32 ``[E, A]`` action values: the act launch takes
   the argmax and explores (``SGW_ACT_QF32``).  It has no ``train_step``, no optimiser and no target network.
 """
@@ -172,6 +174,15 @@ class IQN(nn.Module):
         ``engine=, agent=`` runs ``sgw_turn_iqn_forward``, which reads epoch and turn from the engine's turn state (recordable).  Honours
         ``training``: the noisy layers' effective weights are composed first.  On a HIP device this is one ``sgw_iqn_forward`` call; with
         ``out=`` (an earlier result for the same shapes) it allocates nothing and does not synchronise.  CPU tensors run the torch ops."""
+        B, flat, N, res = self._check_call(states, n_tau, taus, out, cos)
+        dev = flat.device
+        if dev.type != "cuda":
+            return self._quantiles_by_torch(flat, N, taus, res)
+        ws = self.effective_weights(res if out is not None else None)
+        return self._launch_forward(flat, ws, res, taus, key, cos, engine, agent)
+
+    def _check_call(self, states, n_tau, taus, out, cos: bool = False):
+        """What ``quantiles`` and ``forward_fused`` ask of their arguments: ``(B, flat states, N, the IQNOutput to fill)``."""
         B, flat = self._check_states(states)
         N = int(self.n_quantiles if n_tau is None else n_tau)
         A, L = int(self.action_space), int(self.layer_size)
@@ -197,9 +208,12 @@ class IQN(nn.Module):
             if tuple(out.quantiles.shape) != (B, N, A) or out.quantiles.device != dev or out._workspace.numel() * 8 < 4 * B * L or (cos and out.cos is None):
                 raise ValueError("out= was made for other shapes or another device, or without the optional outputs asked for")
             res = out
-        if dev.type != "cuda":
-            return self._quantiles_by_torch(flat, N, taus, res)
-        ws = self.effective_weights(res if out is not None else None)
+        return B, flat, N, res
+
+    def _launch_forward(self, flat, ws, res: IQNOutput, taus=None, key=None, cos: bool = False, engine=None, agent: Optional[int] = None):
+        """One ``sgw_iqn_forward`` call (or ``sgw_turn_iqn_forward``) over checked arguments: ``ws`` are the ten effective weights."""
+        B, N, A = res.quantiles.shape
+        L, dev = int(self.layer_size), flat.device
         for w in ws:
             if w.dtype != torch.float32 or not w.is_contiguous():
                 raise TypeError("the network's parameters must be contiguous float32")
@@ -256,6 +270,37 @@ class IQN(nn.Module):
                 res.cos.copy_(c)
         return res
 
+    # ------------------------------------------------------------------------------------------------ the device path with autograd
+    def forward_fused(self, states, n_tau: Optional[int] = None, *, taus=None, key=None, out: Optional[IQNOutput] = None):
+        """``forward``'s results -- ``(quantiles [B, N, A], taus [B, N, 1])`` -- WITH autograd and without torch's network ops: on a HIP
+        device the quantiles come from ``sgw_iqn_forward`` and their ``backward()`` is one ``sgw_iqn_backward`` call that hands the
+        gradients of the ten effective weights to torch; those are composed with autograd (``weight + sigma * epsilon`` with fresh noise
+        in training mode), so the gradients of ``weight`` and ``sigma_*`` follow by torch's own elementwise ops.  Nothing flows to the
+        states or the taus.  ``taus`` and ``key`` as in ``quantiles``; ``out=`` (an ``IQNOutput``) is filled in place and must stay
+        untouched until ``backward()`` has run: it holds the head layer's activations.  CPU tensors run ``forward``'s torch ops with the
+        given taus."""
+        B, flat, N, res = self._check_call(states, n_tau, taus, out)
+        if flat.device.type != "cuda":
+            return self._forward_by_torch(flat, N, taus)
+        ws = [self.head1.weight, self.head1.bias, self.cos_embedding.weight, self.cos_embedding.bias]
+        for layer in (self.ff_1, self.advantage, self.value):
+            ws += list(layer.effective())
+        quantiles = _FusedQuantiles.apply(self, flat, res, taus, key, *ws)
+        return quantiles, res.taus
+
+    def _forward_by_torch(self, flat, N, taus):
+        """``forward`` on flat states with the taus given (or drawn as ``calc_cos`` draws them)."""
+        B = flat.shape[0]
+        t = (torch.rand(B, N).to(self.pis.device) if taus is None else taus).reshape(B, N, 1)
+        x = torch.relu(self.head1(flat.float()))
+        c = torch.cos(t * self.pis).view(B * N, self.n_cos)
+        e = torch.relu(self.cos_embedding(c)).view(B, N, self.cos_layer_out)
+        z = (x.unsqueeze(1) * e).view(B * N, self.cos_layer_out)
+        y = torch.relu(self.ff_1(z))
+        adv, val = self.advantage(y), self.value(y)
+        out = val + adv - adv.mean(dim=1, keepdim=True)
+        return out.view(B, N, self.action_space), t
+
     def get_qvalues(self, inputs, n_tau: Optional[int] = None, **kwargs):
         """The mean of the quantiles, float32 ``[B, A]`` (``iqn.py:164-167``).  Tensors that require no kernel -- the CPU, or a call under
         autograd with ``requires_grad`` inputs -- take ``forward``; device tensors take ``quantiles`` (same keywords) and come detached."""
@@ -264,6 +309,47 @@ class IQN(nn.Module):
                 quantiles, _ = self.forward(inputs, self.n_quantiles if n_tau is None else n_tau)
                 return quantiles.mean(dim=1)
         return self.quantiles(inputs, n_tau, **kwargs).qvalues
+
+
+class _FusedQuantiles(torch.autograd.Function):
+    """``IQN.forward_fused`` on the device: ``sgw_iqn_forward`` forwards (``res`` keeps ``h`` and the taus), ``sgw_iqn_backward`` backwards."""
+
+    @staticmethod
+    def forward(ctx, net, flat, res, taus, key, *ws):
+        ws = [w.detach().contiguous() for w in ws]
+        net._launch_forward(flat, ws, res, taus, key)
+        ctx.net_sizes = (int(net.layer_size), int(net.action_space))
+        ctx.res = res                         # (h lives in its workspace, the taus in res.taus)
+        ctx.shapes = [tuple(w.shape) for w in ws]
+        ctx.save_for_backward(flat, *ws)
+        return res.quantiles.view_as(res.quantiles)
+
+    @staticmethod
+    def backward(ctx, grad):
+        flat, *ws = ctx.saved_tensors
+        res = ctx.res
+        L, A = ctx.net_sizes
+        B, N = int(res.quantiles.shape[0]), int(res.quantiles.shape[1])
+        dev = flat.device
+        need = ctx.needs_input_grad[5:]
+        grads = [torch.zeros(shape, dtype=torch.float32, device=dev) if wanted else None for shape, wanted in zip(ctx.shapes, need)]
+        if B > 0 and any(need):
+            grad = grad.to(torch.float32).contiguous()
+            D = int(flat.shape[1])
+            space = N_.workspace(int(N_.load().sgw_iqn_backward_workspace_bytes(B, D, L, N, A)), dev)
+            d = N_.SgwIqnBackwardDesc()
+            d.states = flat.data_ptr()
+            (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
+            d.taus, d.h, d.grad_quantiles = res.taus.data_ptr(), res._workspace.data_ptr(), grad.data_ptr()
+            for name, g in zip(("w_head", "b_head", "w_cos", "b_cos", "w_ff", "b_ff", "w_adv", "b_adv", "w_val", "b_val"), grads):
+                if g is not None:
+                    setattr(d, "out_" + name, g.data_ptr())
+            d.workspace, d.workspace_bytes = space.data_ptr(), space.numel() * 8
+            d.n, d.state_stride = B, int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), D)
+            d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = D, L, N, A, N_COS
+            d.state_type = N_.IQN_STATE_U8 if flat.dtype == torch.uint8 else N_.IQN_STATE_F32
+            N_.launch("sgw_iqn_backward", d, dev)
+        return (None, None, None, None, None, *grads)
 
 
 class IQNActor(BaseModel):
