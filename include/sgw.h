@@ -1101,6 +1101,55 @@ int sgw_iqn_backward(const sgw_iqn_backward_desc* desc, void* stream);
 /* Bytes of workspace a call needs (0 for no rows); a negative code for n outside [0, 2^40) or a size outside sgw_iqn_backward's ranges. */
 int64_t sgw_iqn_backward_workspace_bytes(int64_t n, int32_t in_features, int32_t layer_size, int32_t num_quantiles, int32_t num_actions);
 
+/* ---- The noisy layers' weights (sorrel/models/pytorch/layers.py:9-65: NoisyLinear.forward's epsilon.normal_() and
+ * weight + sigma * epsilon for the weight and the bias of IQN's three noisy layers in each of the three network calls of
+ * iRainbowModel.train_step -- 18 normal_, 18 mul and 18 add launches a step -- and autograd's grad * epsilon for the six sigma tensors
+ * behind loss.backward(); one launch over a table of tensors each way) ----
+ * A call serves num_jobs <= SGW_NOISY_MAX_JOBS jobs; job k is one tensor of count float32 elements.  All tensors are contiguous float32,
+ * aligned to 4 bytes (no more is asked: a bias of one element lies anywhere).
+ *   mode = SGW_NOISY_FORWARD, per element i of a job:
+ *     eps_i      = eps_in[i] where eps_in is given; otherwise drawn KEYED, a pure function of (seed, draw, tensor_id, i):
+ *                  w = Philox4x32-10(ctr = {i >> 2, draw & 0xffffffff, draw >> 32, tensor_id << 4 | SGW_STREAM_NOISE}, key = {seed lo, seed hi});
+ *                  one block gives four consecutive elements by Box-Muller over its word pairs (w_a, w_b) = (w0, w1) for i & 3 = 0, 1 and
+ *                  (w2, w3) for i & 3 = 2, 3:  u1 = (float)((w_a >> 8) + 1) * 2^-24 in (0, 1],  u2 = (float)(w_b >> 8) * 2^-24 in [0, 1),
+ *                  r = sqrtf(-2 * logf(u1)),  arg = (float)(2 pi) * u2 (a float32 product),  eps = r * cosf(arg) for even i and r * sinf(arg) for
+ *                  odd i; logf, cosf and sinf are the device library's full-precision ones.  |eps| <= sqrt(48 ln 2) = 5.77.  Not consumed:
+ *                  the same key gives the same normals whichever jobs share the call and wherever the job stands in the table.
+ *     out_eff[i] = weight[i] + (sigma[i] * eps_i): the product is rounded, then the sum (no fused multiply-add), which is torch's
+ *                  self.weight + self.sigma_weight * self.epsilon_weight bit for bit.
+ *     out_eps[i] = eps_i, where out_eps is given (what the backward needs of a drawn job).
+ *     weight, sigma and out_eff are required; grad_eff and out_grad_sigma must be NULL.
+ *   mode = SGW_NOISY_BACKWARD, per element:  out_grad_sigma[i] = grad_eff[i] * eps_in[i], one rounding; eps_in (the forward's eps), grad_eff
+ *     and out_grad_sigma are required, the forward's pointers must be NULL, tensor_id is ignored.  (The gradient of weight IS grad_eff.)
+ * Non-finite inputs give what IEEE arithmetic gives, in that element only.  A job of count 0 and a call of num_jobs 0 write nothing.
+ * Jobs past num_jobs are ignored.  No atomics.  Needs no engine; all pointers are device pointers; outputs must not overlap anything.
+ * Asynchronous on `stream`; a NULL required pointer, a pointer the mode does not take, a misaligned pointer, count outside [0, 2^32],
+ * tensor_id outside [0, 2^28), num_jobs outside [0, SGW_NOISY_MAX_JOBS], an unknown mode and a non-zero reserved field are SGW_EINVAL
+ * with the reason in sgw_last_error(), before anything is launched. */
+enum { SGW_STREAM_NOISE = 12 };      /* index = element of the tensor, turn / env slots = low / high word of `draw`, epoch slot = tensor_id: sgw_noisy_weights' normals (the thirteenth stream; an enumerator) */
+#define SGW_NOISY_MAX_JOBS 24        /* a learner's step: 18 forward (3 network calls x 6 tensors), 6 backward */
+#define SGW_NOISY_FORWARD 0
+#define SGW_NOISY_BACKWARD 1
+typedef struct sgw_noisy_job {
+    const float* weight;         /* forward: [count] */
+    const float* sigma;          /* forward: [count] */
+    const float* eps_in;         /* forward: [count], or NULL: drawn; backward: [count], the forward's eps */
+    const float* grad_eff;       /* backward: [count] */
+    float* out_eff;              /* forward: [count] */
+    float* out_eps;              /* forward: [count], or NULL */
+    float* out_grad_sigma;       /* backward: [count] */
+    int64_t count;
+    int32_t tensor_id;
+    int32_t reserved;            /* reserved: 0 */
+} sgw_noisy_job;
+typedef struct sgw_noisy_weights_desc {
+    sgw_noisy_job jobs[SGW_NOISY_MAX_JOBS];
+    uint64_t seed, draw;         /* the drawn normals' key, with each job's tensor_id */
+    int32_t num_jobs, mode;
+    int32_t reserved0, reserved1;    /* reserved: 0 */
+} sgw_noisy_weights_desc;
+int sgw_noisy_weights(const sgw_noisy_weights_desc* desc, void* stream);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

@@ -43,6 +43,9 @@ IQN_MAX_LAYER, IQN_MAX_ACTIONS, IQN_N_COS = 256, 64, 64      # of sgw_iqn_forwar
 ADAM_CLIP_NONE, ADAM_CLIP_NORM, ADAM_CLIP_COEF = 0, 1, 2
 ADAM_ZERO_GRADS = 1
 ADAM_MAX_TENSORS, ADAM_CHUNK = 4096, 4096
+STREAM_NOISE = 12            # sgw_noisy_weights' normals: index = element, turn / env slots = the draw counter's words, epoch slot = tensor_id
+NOISY_MAX_JOBS = 24
+NOISY_FORWARD, NOISY_BACKWARD = 0, 1
 POLICY_INVALID_ACTION = 255  # the action of a row torch's Categorical would raise for (its log-probability and entropy are NaN)
 
 
@@ -295,6 +298,28 @@ class SgwAdamStepDesc(C.Structure):
     ]
 
 
+class SgwNoisyJob(C.Structure):
+    """Mirror of ``struct sgw_noisy_job``: one tensor of an ``sgw_noisy_weights`` call."""
+
+    _fields_ = [
+        ("weight", C.c_void_p), ("sigma", C.c_void_p), ("eps_in", C.c_void_p), ("grad_eff", C.c_void_p),
+        ("out_eff", C.c_void_p), ("out_eps", C.c_void_p), ("out_grad_sigma", C.c_void_p),
+        ("count", C.c_int64),
+        ("tensor_id", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SgwNoisyWeightsDesc(C.Structure):
+    """Mirror of ``struct sgw_noisy_weights_desc``: one ``sgw_noisy_weights`` call."""
+
+    _fields_ = [
+        ("jobs", SgwNoisyJob * NOISY_MAX_JOBS),
+        ("seed", C.c_uint64), ("draw", C.c_uint64),
+        ("num_jobs", C.c_int32), ("mode", C.c_int32),
+        ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -367,6 +392,7 @@ PROTOTYPES = {
     "sgw_turn_iqn_forward": (_rc, [_vp, _i32, C.POINTER(SgwIqnForwardDesc), _vp]),
     "sgw_iqn_backward": (_rc, [C.POINTER(SgwIqnBackwardDesc), _vp]),
     "sgw_iqn_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "sgw_noisy_weights": (_rc, [C.POINTER(SgwNoisyWeightsDesc), _vp]),
     "sgw_adam_plan_bytes": (_i64, [_i64, _i64]),
     "sgw_adam_plan": (_rc, [C.POINTER(SgwAdamTensor), _i64, _i32, _vp, _i64, C.POINTER(SgwAdamPlanInfo)]),
     "sgw_adam_step": (_rc, [C.POINTER(SgwAdamStepDesc), _vp]),

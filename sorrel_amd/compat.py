@@ -19,7 +19,7 @@ or, without touching the script at all::
 ``install`` registers a meta-path finder that answers every ``sorrel`` / ``sorrel.*`` import with the ``sorrel_amd``
 module of the same relative name (the SAME module object: ``sorrel.environment.Environment is
 sorrel_amd.environment.Environment``).  Parts of the reference outside the hot path this package rebuilds (models beyond
-``BaseModel`` / ``RandomModel``, logging, the CLI, NodeWorld, chess) do not exist here; importing
+``BaseModel`` / ``RandomModel`` / ``PyTorchIQN``, logging, the CLI, NodeWorld, chess) do not exist here; importing
 them fails with a ``ModuleNotFoundError`` that says so.  If a real ``sorrel`` distribution is importable, ``install``
 refuses to shadow it unless ``force=True``.
 """
@@ -48,7 +48,7 @@ OUT_OF_SCOPE = {
     "threadsafe": "RLock wrappers around a shared model",
     "worlds.nodeworld": "the graph world for LLM agents",
     "worlds.base_world": None,       # (the abstract World lives in sorrel_amd.worlds.gridworld; aliased below)
-    "models.pytorch": "IQN / PPO / ViT policy learning (PPO's data side exists: sorrel_amd.buffers.RolloutBuffer and Buffer.returns / TurnBuffer.returns; so does ActorCritic.act's sampling: models.ActionProbs / ActionLogits, sgw_policy_sample; and the clipped loss of train_step's k_epochs loop with its gradients: sorrel_amd.losses.ppo_loss / ppo_loss_terms, sgw_ppo_loss; and IQN's quantile Huber loss of iRainbowModel.train_step with its gradient: sorrel_amd.losses.iqn_loss / iqn_loss_terms, sgw_iqn_loss; and what follows loss.backward() -- clip_grad_norm_, Adam, soft_update: sorrel_amd.optim.FusedAdam, sgw_adam_step -- the networks and the learner class stay the user's)",
+    "models.pytorch": "IQN / PPO / ViT policy learning (PPO's data side exists: sorrel_amd.buffers.RolloutBuffer and Buffer.returns / TurnBuffer.returns; so does ActorCritic.act's sampling: models.ActionProbs / ActionLogits, sgw_policy_sample; and the clipped loss of train_step's k_epochs loop with its gradients: sorrel_amd.losses.ppo_loss / ppo_loss_terms, sgw_ppo_loss; and IQN's quantile Huber loss of iRainbowModel.train_step with its gradient: sorrel_amd.losses.iqn_loss / iqn_loss_terms, sgw_iqn_loss; and what follows loss.backward() -- clip_grad_norm_, Adam, soft_update: sorrel_amd.optim.FusedAdam, sgw_adam_step; the IQN learner itself -- iRainbowModel, which the examples import as PyTorchIQN -- is sorrel_amd.models.PyTorchIQN, so `from sorrel.models import PyTorchIQN` works; PPO's and ViT's networks and learner classes stay the user's)",
     "models.human_player": "interactive play",
     "models.llm": "LLM clients",
     "examples.chess": "chess",

@@ -80,6 +80,7 @@ namespace {
 #include "adam_step.h"
 #include "iqn_forward.h"
 #include "iqn_backward.h"
+#include "noisy.h"
 
 // ---------------------------------------------------------------- host side
 #include "options.h"
@@ -101,7 +102,7 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(SGW_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss, sgw_adam_step, sgw_iqn_forward) ask of their arguments
+// what the engine-free entry points (sgw_sample, sgw_returns, sgw_policy_sample, sgw_ppo_loss, sgw_iqn_loss, sgw_adam_step, sgw_iqn_forward, sgw_noisy_weights) ask of their arguments
 inline uintptr_t at(const void* q) { return reinterpret_cast<uintptr_t>(q); }
 // is any of these pointers off the alignment `mask` + 1?  (NULL, an optional argument or one of another type, is aligned to everything)
 inline bool misaligned(const uintptr_t mask, std::initializer_list<const void*> ptrs) {
@@ -1696,6 +1697,52 @@ int sgw_iqn_backward(const sgw_iqn_backward_desc* d, void* stream) {
         hipLaunchKernelGGL(iqn_wgrad_kernel, dim3((unsigned)ceil_div(tiles, kBwdWaves)), dim3(64 * kBwdWaves), 0, s, g);
         HIP_TRY(hipGetLastError());
     }
+    return SGW_OK;
+}
+
+// ---------------------------------------------------------------- the noisy layers' weights (noisy.h)
+int sgw_noisy_weights(const sgw_noisy_weights_desc* d, void* stream) {
+    const char* who = "sgw_noisy_weights";
+    if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
+    if (d->mode != SGW_NOISY_FORWARD && d->mode != SGW_NOISY_BACKWARD) return fail(SGW_EINVAL, "%s: unknown mode %d", who, d->mode);
+    if (d->num_jobs < 0 || d->num_jobs > SGW_NOISY_MAX_JOBS) return fail(SGW_EINVAL, "%s: num_jobs = %d outside [0, %d]", who, d->num_jobs, SGW_NOISY_MAX_JOBS);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
+    const bool backward = d->mode == SGW_NOISY_BACKWARD;
+    NoisyParams p{};
+    int64_t chunks = 0;
+    for (int k = 0; k < SGW_NOISY_MAX_JOBS; ++k) {
+        NoisyJob& o = p.job[k];
+        o.chunk0 = INT32_MAX;
+        if (k >= d->num_jobs) continue;
+        const sgw_noisy_job& j = d->jobs[k];
+        if (backward) {
+            if (!j.grad_eff || !j.eps_in || !j.out_grad_sigma) return fail(SGW_EINVAL, "%s: job %d: grad_eff, eps_in and out_grad_sigma must not be NULL (backward)", who, k);
+            if (j.weight || j.sigma || j.out_eff || j.out_eps) return fail(SGW_EINVAL, "%s: job %d: weight, sigma, out_eff and out_eps must be NULL (backward)", who, k);
+        } else {
+            if (!j.weight || !j.sigma || !j.out_eff) return fail(SGW_EINVAL, "%s: job %d: weight, sigma and out_eff must not be NULL (forward)", who, k);
+            if (j.grad_eff || j.out_grad_sigma) return fail(SGW_EINVAL, "%s: job %d: grad_eff and out_grad_sigma must be NULL (forward)", who, k);
+            if (j.tensor_id < 0 || j.tensor_id >= (1 << 28)) return fail(SGW_EINVAL, "%s: job %d: tensor_id = %d outside [0, 2^28)", who, k, j.tensor_id);
+        }
+        if (j.count < 0 || j.count > ((int64_t)1 << 32)) return fail(SGW_EINVAL, "%s: job %d: count = %lld outside [0, 2^32]", who, k, (long long)j.count);
+        if (j.reserved) return fail(SGW_EINVAL, "%s: job %d: reserved fields must be 0", who, k);
+        if (misaligned(3, {j.weight, j.sigma, j.eps_in, j.grad_eff, j.out_eff, j.out_eps, j.out_grad_sigma}))
+            return fail(SGW_EINVAL, "%s: job %d: misaligned float32 pointer", who, k);
+        o.a = backward ? j.grad_eff : j.weight;
+        o.b = j.sigma;
+        o.eps = j.eps_in;
+        o.out = backward ? j.out_grad_sigma : j.out_eff;
+        o.out_eps = j.out_eps;
+        o.count = j.count;
+        o.c3 = ((uint32_t)j.tensor_id << 4) | (uint32_t)SGW_STREAM_NOISE;
+        o.chunk0 = (int32_t)chunks;               // (at most 24 * 2^22 chunks)
+        chunks += ceil_div(j.count, kNoisyChunk);
+    }
+    if (chunks == 0) return SGW_OK;
+    p.seed_lo = (uint32_t)d->seed; p.seed_hi = (uint32_t)(d->seed >> 32);
+    p.draw_lo = (uint32_t)d->draw; p.draw_hi = (uint32_t)(d->draw >> 32);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (backward) LAUNCH_TRY(noisy_kernel<true>, (unsigned)chunks, s, p);
+    else LAUNCH_TRY(noisy_kernel<false>, (unsigned)chunks, s, p);
     return SGW_OK;
 }
 

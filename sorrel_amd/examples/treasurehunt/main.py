@@ -1,7 +1,17 @@
-"""Run batched Treasurehunt rollouts: ``python -m sorrel_amd.examples.treasurehunt.main``."""
+"""Run batched Treasurehunt rollouts: ``python -m sorrel_amd.examples.treasurehunt.main [--model iqn]``.
+
+The default agents act at random (``RandomModel``: the whole epoch is one engine call).  ``--model iqn`` gives every agent a
+``sorrel_amd.models.PyTorchIQN`` built from ``config.model.*`` with the reference's keys (``sorrel/examples/treasurehunt/env.py:80-99``): the
+agents act through the network, fill its replay ring and learn after every epoch."""
+import sys
+
 from sorrel_amd.examples.treasurehunt.entities import EmptyEntity
 from sorrel_amd.examples.treasurehunt.env import TreasurehuntEnv
 from sorrel_amd.examples.treasurehunt.world import TreasurehuntWorld
+
+#: ``config.model`` keys ``iqn_model_factory`` hands to ``PyTorchIQN`` (the reference's), and the reference example's values
+IQN_DEFAULTS = dict(layer_size=250, epsilon=0.6, n_frames=5, n_step=3, sync_freq=200, model_update_freq=4, batch_size=64, memory_size=1024,
+                    LR=0.00025, TAU=0.001, GAMMA=0.99, n_quantiles=12)
 
 
 def make_config(height=21, width=21, num_agents=2, radius=2, spawn_prob=0.005, epochs=2, max_turns=100):
@@ -13,9 +23,40 @@ def make_config(height=21, width=21, num_agents=2, radius=2, spawn_prob=0.005, e
     }
 
 
+def iqn_model_factory(config, num_envs, device=None, seed=0):
+    """A ``model_factory`` for ``TreasurehuntEnv``: every agent gets its own ``PyTorchIQN`` from ``config["model"]`` (``IQN_DEFAULTS`` for
+    the keys it leaves out), with a replay ring over ``num_envs`` envs; agent ``k``'s seed is ``seed + k``."""
+    from sorrel_amd.models import PyTorchIQN
+
+    model = config["model"]
+    args = {key: model[key] if key in model else default for key, default in IQN_DEFAULTS.items()}
+    made = []
+
+    def factory(input_size, action_space):
+        made.append(PyTorchIQN(input_size, action_space, device=device, seed=seed + len(made), num_envs=num_envs, **args))
+        return made[-1]
+
+    return factory
+
+
+def make_env(config, num_envs, model="random", device=None, seed=0):
+    """The example's environment: ``model`` is ``"random"`` or ``"iqn"``."""
+    if model not in ("random", "iqn"):
+        raise ValueError(f"unknown model {model!r}: random or iqn")
+    world = TreasurehuntWorld(config=config, default_entity=EmptyEntity(), num_envs=num_envs, **({} if device is None else {"device": device}))
+    if model == "random":
+        return TreasurehuntEnv(world, config)
+    env = TreasurehuntEnv(world, config, model_factory=iqn_model_factory(config, num_envs, device=world.device, seed=seed))
+    for slot, agent in enumerate(env.agents):
+        agent.model.bind(env, slot)
+    return env
+
+
 if __name__ == "__main__":
+    argv = sys.argv[1:]
+    kind = argv[argv.index("--model") + 1] if "--model" in argv else "random"
     config = make_config()
-    world = TreasurehuntWorld(config=config, default_entity=EmptyEntity(), num_envs=4096)
-    env = TreasurehuntEnv(world, config)
+    env = make_env(config, 4096 if kind == "random" else 256, kind)
     for epoch, m in enumerate(env.run_experiment()):
-        print(f"epoch {epoch}: mean total_reward over {int(m['envs'])} envs = {m['mean_total_reward']:.3f}")
+        print(f"epoch {epoch}: mean total_reward over {int(m['envs'])} envs = {m['mean_total_reward']:.3f}" +
+              (f", loss = {m['loss']:.5f}" if kind == "iqn" else ""))

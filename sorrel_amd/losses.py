@@ -30,6 +30,8 @@ With ``sorrel_amd.models.iqn.IQN`` the three network calls run without torch's n
     q_next_local = local.quantiles(next_states).quantiles; q_next_target = target.quantiles(next_states).quantiles
     q_expected, taus = local.forward_fused(states)
     loss = iqn_loss(q_expected, taus, q_next_local, q_next_target, actions, rewards, dones, valid, GAMMA ** n_step); loss.backward(); optimizer.step()
+
+``sorrel_amd.models.PyTorchIQN`` (``models/iqn_learner.py``) is the learner class over these calls: its ``train_step()`` is this step without autograd.
 """
 from __future__ import annotations
 

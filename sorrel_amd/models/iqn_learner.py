@@ -1,0 +1,316 @@
+"""The IQN learner (``sorrel/models/pytorch/iqn.py:179-443``: ``iRainbowModel``, which the reference's examples import as ``PyTorchIQN``): two
+``IQN`` networks, Adam, a replay ``Buffer``, ``take_action``, ``train_step``, ``start_epoch_action``, ``save`` / ``load``.
+
+* On the CPU ``train_step`` runs the reference's lines as torch ops: the baseline, and what the reference returns (a 0-d float32 ndarray).
+* On a HIP device ``train_step`` is a fixed sequence of native calls over buffers allocated once, without autograd:
+  ``sgw_sample`` (``ReplaySampler``), one ``sgw_noisy_weights`` call that composes the effective noisy weights of the three network calls
+  (18 tensors; ``sorrel_amd/csrc/noisy.h``), three ``sgw_iqn_forward`` calls, ``sgw_iqn_loss``, one ``sgw_iqn_backward`` that writes into the
+  parameters' persistent ``.grad`` tensors (the gradient of a noisy layer's ``weight`` IS that of its effective weight), one
+  ``sgw_noisy_weights`` call in backward mode for the six ``sigma_*.grad``, and ``FusedAdam.step()`` (clipping, Adam and the soft update).
+  The taus and the noise are keyed by (``seed``, the count of steps done, the network call's index 0..2): a step is reproducible from
+  its number.  The loss comes back as a 0-d float32 device tensor, a view of a buffer the next call overwrites; nothing synchronises.
+* ``take_action`` evaluates ``qnetwork_local`` with the MEAN weights (the reference acts in eval mode) and returns the float32 ``[E, A]``
+  action values: the act launch takes the argmax and explores with ``epsilon``.  It never toggles ``training``."""
+from __future__ import annotations
+
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from sorrel_amd import _native as N_
+from sorrel_amd.buffers import Buffer, ReplaySampler
+from sorrel_amd.models.base_model import BaseModel
+from sorrel_amd.models.iqn import IQN, N_COS, IQNOutput
+from sorrel_amd.optim import FusedAdam
+from sorrel_amd.spec import resolve_device
+
+NOISY_LAYERS = ("ff_1", "advantage", "value")
+N_NOISE = 2 * len(NOISY_LAYERS)               # eps tensors of one network call: (weight, bias) of each noisy layer, in that order
+N_CALLS = 3                                   # local on next_states, target on next_states, local on states
+
+
+def _noisy_tensors(net: IQN):
+    """``(weight-like, its sigma)`` of the six noisy tensors of ``net``, in the order the noise is drawn."""
+    out = []
+    for name in NOISY_LAYERS:
+        layer = getattr(net, name)
+        out += [(layer.weight, layer.sigma_weight), (layer.bias, layer.sigma_bias)]
+    return out
+
+
+def _network_torch(net: IQN, flat, n_tau: int, taus=None, eps=None, mean: bool = False):
+    """``IQN.forward``'s lines on flat states: the taus as given or drawn as ``calc_cos`` draws them; the noisy layers with the six ``eps``
+    tensors given, with fresh ``normal_()`` noise (``eps`` None, as ``NoisyLinear.forward`` in training mode), or with the mean weights."""
+    B = flat.shape[0]
+    t = torch.rand(B, n_tau).unsqueeze(-1).to(net.pis.device) if taus is None else taus.reshape(B, n_tau, 1)
+    x = torch.relu(net.head1(flat))
+    cos = torch.cos(t * net.pis).view(B * n_tau, net.n_cos)
+    cos = torch.relu(net.cos_embedding(cos))
+    cos_x = cos.view(B, n_tau, net.cos_layer_out)
+    x = (x.unsqueeze(1) * cos_x).view(B * n_tau, net.cos_layer_out)
+
+    def noisy(k, x):
+        layer = getattr(net, NOISY_LAYERS[k])
+        if mean:
+            return F.linear(x, layer.weight, layer.bias)
+        if eps is None:
+            layer.epsilon_weight.normal_()
+            layer.epsilon_bias.normal_()
+        else:
+            layer.epsilon_weight.copy_(eps[2 * k])
+            layer.epsilon_bias.copy_(eps[2 * k + 1])
+        weight = layer.weight + layer.sigma_weight * layer.epsilon_weight
+        bias = layer.bias + layer.sigma_bias * layer.epsilon_bias
+        return F.linear(x, weight, bias)
+
+    x = torch.relu(noisy(0, x))
+    advantage = noisy(1, x)
+    value = noisy(2, x)
+    out = value + advantage - advantage.mean(dim=1, keepdim=True)
+    return out.view(B, n_tau, net.action_space), t
+
+
+class _DeviceStep:
+    """What the device path of ``train_step`` allocates once: the three sets of effective weights, the kept noise, the three forwards'
+    outputs, the loss terms, the backward's workspace and the descriptors whose pointers do not change."""
+
+    __slots__ = ("key", "eff", "eps", "outs", "loss", "space", "noise_fwd", "noise_bwd", "bwd")
+
+
+class iRainbowModel(BaseModel):
+    """The reference's ``iRainbowModel`` (its constructor, argument names and defaults), plus ``num_envs`` for the batched replay ring."""
+
+    def __init__(self, input_size: Sequence[int], action_space: int, layer_size: int, epsilon: float, device, seed: int, n_frames: int,
+                 n_step: int = 3, sync_freq: int = 200, model_update_freq: int = 4, batch_size: int = 64, memory_size: int = 1024,
+                 LR: float = 0.001, TAU: float = 0.001, GAMMA: float = 0.99, n_quantiles: int = 12, num_envs: int = 1) -> None:
+        super().__init__(input_size, action_space, memory_size=0, epsilon=epsilon)
+        self.layer_size = layer_size
+        self.device = resolve_device(device)
+        self.key_seed = int(seed)
+        self.seed = torch.manual_seed(seed)
+        self.n_frames, self.TAU, self.n_quantiles, self.GAMMA = n_frames, TAU, n_quantiles, GAMMA
+        self.batch_size, self.n_step, self.sync_freq, self.model_update_freq = batch_size, n_step, sync_freq, model_update_freq
+        shape = tuple(input_size) if isinstance(input_size, Sequence) else (input_size,)
+        self.qnetwork_local = IQN(shape, action_space, layer_size, seed, n_quantiles, n_frames, device=self.device)
+        self.qnetwork_target = IQN(shape, action_space, layer_size, seed, n_quantiles, n_frames, device=self.device)
+        self.models = {"local": self.qnetwork_local, "target": self.qnetwork_target}
+        self.optimizer = FusedAdam(self.qnetwork_local.parameters(), lr=LR, max_grad_norm=1, target_params=self.qnetwork_target.parameters(), tau=TAU)
+        self.memory = Buffer(capacity=memory_size, obs_shape=(int(np.array(shape).prod()),), n_frames=n_frames, num_envs=num_envs, device=self.device)
+        self.steps_done = 0                   # the count of gated steps: the key of a step's taus and noise
+        self._env, self._slot, self._out = None, 0, None
+        self._sampler: Optional[ReplaySampler] = None
+        self._step: Optional[_DeviceStep] = None
+        self._loss32 = torch.zeros((), dtype=torch.float32, device=self.device)
+
+    def __str__(self):
+        return f"iRainbowModel(input_size={np.array(self.input_size).prod() * self.n_frames},action_space={self.action_space})"
+
+    # ------------------------------------------------------------------------------------------------------------ acting
+    def bind(self, env, slot: int) -> "iRainbowModel":
+        """Whose turn the taus of ``take_action`` are keyed by (as ``IQNActor.bind``)."""
+        self._env, self._slot = env, int(slot)
+        return self
+
+    def _mean_weights(self, net: IQN):
+        ws = [net.head1.weight, net.head1.bias, net.cos_embedding.weight, net.cos_embedding.bias]
+        for name in NOISY_LAYERS:
+            layer = getattr(net, name)
+            ws += [layer.weight, layer.bias]
+        return [w.detach() for w in ws]
+
+    def take_action(self, state):
+        """The float32 ``[E, A]`` action values of ``qnetwork_local`` with the mean weights, detached."""
+        net = self.qnetwork_local
+        B = int(state.shape[0])
+        if state.device.type != "cuda":
+            with torch.no_grad():
+                q, _ = _network_torch(net, state.reshape(B, -1).float(), self.n_quantiles, mean=True)
+                return q.mean(dim=1)
+        if self._out is None or self._out.quantiles.shape[0] != B or self._out.quantiles.device != state.device:
+            self._out = IQNOutput(B, net.n_quantiles, net.action_space, net.layer_size, state.device)
+        _, flat, _, res = net._check_call(state, None, None, self._out)
+        ws = self._mean_weights(net)
+        env = self._env
+        if env is None:
+            return net._launch_forward(flat, ws, res).qvalues
+        eng = env._ensure_engine()
+        if getattr(env, "_mixed", False):
+            eng = env._agent_engine[self._slot]
+        if env._turn_capture:
+            return net._launch_forward(flat, ws, res, engine=eng, agent=self._slot).qvalues
+        key = {"seed": int(eng.spec.seed), "epoch": int(env.epoch), "turn": int(env.turn), "num_envs": int(eng.num_envs), "agent0": self._slot,
+               "first_env": int(eng.first_env_id)}
+        return net._launch_forward(flat, ws, res, key=key).qvalues
+
+    # ------------------------------------------------------------------------------------------------------------ the epoch hooks
+    def start_epoch_action(self, **kwargs) -> None:
+        self.memory.add_empty()
+        if kwargs["epoch"] % self.sync_freq == 0:
+            self.qnetwork_target.load_state_dict(self.qnetwork_local.state_dict())
+
+    def end_epoch_action(self, **kwargs) -> None:
+        pass
+
+    def soft_update(self) -> None:
+        """``target = TAU * local + (1 - TAU) * target`` (what ``train_step`` does inside the optimiser's call)."""
+        for target_param, local_param in zip(self.qnetwork_target.parameters(), self.qnetwork_local.parameters()):
+            target_param.data.copy_(self.TAU * local_param.data + (1.0 - self.TAU) * target_param.data)
+
+    # ------------------------------------------------------------------------------------------------------------ files
+    def save(self, file_path) -> None:
+        """The reference's checkpoint: ``{"local": state_dict, "target": state_dict, "optim": the optimiser's}`` through ``torch.save``."""
+        directory = os.path.dirname(str(file_path))
+        if directory:
+            os.makedirs(directory, exist_ok=True)
+        torch.save({**{key: value.state_dict() for key, value in self.models.items()}, "optim": self.optimizer.state_dict()}, file_path)
+
+    def load(self, file_path) -> None:
+        checkpoint = torch.load(file_path, map_location=self.device)
+        for key in self.models:
+            self.models[key].load_state_dict(checkpoint[key])
+        self.optimizer.load_state_dict(checkpoint["optim"])
+
+    # ------------------------------------------------------------------------------------------------------------ the step
+    def train_step(self, *, batch=None, taus=None, noise=None):
+        """One update (``iqn.py:322-412``), gated by ``len(memory) > batch_size``.  Keyword-only test hooks override the draws on both
+        paths: ``batch`` = the six-tuple ``Buffer.sample`` returns, ``taus`` = three ``[B, N]`` tensors and ``noise`` = 18 eps tensors, both in
+        the order of the network calls (local on next_states, target on next_states, local on states; within a call ``ff_1``,
+        ``advantage``, ``value``, weight before bias).  Returns the loss: on the CPU a 0-d float32 ndarray, on a HIP device a 0-d float32
+        tensor that the next call overwrites (0 below the gate)."""
+        if taus is not None and len(taus) != N_CALLS:
+            raise ValueError(f"taus= takes {N_CALLS} tensors, one per network call")
+        if noise is not None and len(noise) != N_CALLS * N_NOISE:
+            raise ValueError(f"noise= takes {N_CALLS * N_NOISE} tensors, six per network call")
+        if self.device.type != "cuda":
+            return self._train_step_torch(batch, taus, noise)
+        if not len(self.memory) > self.batch_size:
+            self._loss32.zero_()
+            return self._loss32
+        return self._train_step_device(batch, taus, noise)
+
+    def _train_step_torch(self, batch, taus, noise):
+        from sorrel_amd.losses import _iqn_loss_torch         # (losses imports this package's base_model: not at module level)
+
+        loss = torch.tensor(0.0)
+        self.optimizer.zero_grad(set_to_none=True)        # (torch's default, which the reference's optimizer.zero_grad() takes)
+        if len(self.memory) > self.batch_size:
+            if batch is None:
+                batch = self.memory.sample(batch_size=self.batch_size)
+            states, actions, rewards, next_states, dones, valid = (torch.as_tensor(x) for x in batch)
+            local, target, n = self.qnetwork_local, self.qnetwork_target, self.n_quantiles
+            tau = [None] * N_CALLS if taus is None else list(taus)
+            eps = [None] * N_CALLS if noise is None else [noise[c * N_NOISE:(c + 1) * N_NOISE] for c in range(N_CALLS)]
+            B = states.shape[0]
+            q_next_local, _ = _network_torch(local, next_states.view(B, -1), n, tau[0], eps[0])
+            q_next_target, _ = _network_torch(target, next_states.view(B, -1), n, tau[1], eps[1])
+            q_expected, t = _network_torch(local, states.view(B, -1), n, tau[2], eps[2])
+            loss = _iqn_loss_torch(q_expected, t, q_next_local, q_next_target, actions, rewards, dones, valid, self.GAMMA ** self.n_step)[0]
+            loss.backward()
+            self.optimizer.step()             # clip_grad_norm_(.., 1), Adam, soft_update(): the reference's lines (optim._adam_step_torch)
+            self.steps_done += 1
+        return loss.detach().numpy()
+
+    def _prepare(self) -> _DeviceStep:
+        """The device step's buffers and descriptors, rebuilt only when a parameter or a gradient has moved."""
+        from sorrel_amd.losses import IQNLoss
+
+        local, target = self.qnetwork_local, self.qnetwork_target
+        params = list(local.parameters())
+        for p in params:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        key = tuple(p.data_ptr() for p in params) + tuple(p.grad.data_ptr() for p in params) + tuple(p.data_ptr() for p in target.parameters())
+        st = self._step
+        if st is not None and st.key == key:
+            return st
+        dev, B, Nq, A, L = self.device, self.batch_size, self.n_quantiles, self.action_space, self.layer_size
+        D = local.head1.in_features
+        if st is None:
+            st = _DeviceStep()
+            st.eff = [[torch.empty_like(w) for w, _ in _noisy_tensors(local)] for _ in range(N_CALLS)]
+            st.eps = [torch.empty_like(w) for w, _ in _noisy_tensors(local)]
+            st.outs = [IQNOutput(B, Nq, A, L, dev) for _ in range(N_CALLS)]
+            st.loss = IQNLoss(st.outs[2].quantiles)
+            st.space = N_.workspace(int(N_.load().sgw_iqn_backward_workspace_bytes(B, D, L, Nq, A)), dev)
+        st.key = key
+        # the forward composition: job c * 6 + t = tensor t of network call c (the target network in call 1)
+        f = N_.SgwNoisyWeightsDesc()
+        f.mode, f.num_jobs, f.seed = N_.NOISY_FORWARD, N_CALLS * N_NOISE, self.key_seed & 0xFFFFFFFFFFFFFFFF
+        for c, net in enumerate((local, target, local)):
+            for t, (w, s) in enumerate(_noisy_tensors(net)):
+                job = f.jobs[c * N_NOISE + t]
+                job.weight, job.sigma, job.out_eff, job.count, job.tensor_id = w.data_ptr(), s.data_ptr(), st.eff[c][t].data_ptr(), w.numel(), c * N_NOISE + t
+                if c == N_CALLS - 1:
+                    job.out_eps = st.eps[t].data_ptr()        # the backward needs the noise of the q_expected call, drawn or given
+        st.noise_fwd = f
+        g = N_.SgwNoisyWeightsDesc()
+        g.mode, g.num_jobs = N_.NOISY_BACKWARD, N_NOISE
+        for t, (w, s) in enumerate(_noisy_tensors(local)):
+            job = g.jobs[t]
+            job.grad_eff, job.eps_in, job.out_grad_sigma, job.count = w.grad.data_ptr(), st.eps[t].data_ptr(), s.grad.data_ptr(), w.numel()
+        st.noise_bwd = g
+        d = N_.SgwIqnBackwardDesc()
+        ws = self._weights(local, st.eff[2])
+        (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
+        res = st.outs[2]
+        d.taus, d.h, d.grad_quantiles = res.taus.data_ptr(), res._workspace.data_ptr(), st.loss.grad_expected.data_ptr()
+        grads = [local.head1.weight.grad, local.head1.bias.grad, local.cos_embedding.weight.grad, local.cos_embedding.bias.grad]
+        grads += [w.grad for w, _ in _noisy_tensors(local)]
+        (d.out_w_head, d.out_b_head, d.out_w_cos, d.out_b_cos, d.out_w_ff, d.out_b_ff, d.out_w_adv, d.out_b_adv, d.out_w_val, d.out_b_val) = (
+            x.data_ptr() for x in grads)
+        d.workspace, d.workspace_bytes = st.space.data_ptr(), st.space.numel() * 8
+        d.n, d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = B, D, L, Nq, A, N_COS
+        d.state_type = N_.IQN_STATE_F32
+        st.bwd = d
+        self._step = st
+        return st
+
+    @staticmethod
+    def _weights(net: IQN, eff):
+        return [net.head1.weight.detach(), net.head1.bias.detach(), net.cos_embedding.weight.detach(), net.cos_embedding.bias.detach(), *eff]
+
+    def _train_step_device(self, batch, taus, noise):
+        from sorrel_amd.losses import iqn_loss_terms
+
+        dev, B = self.device, self.batch_size
+        local, target = self.qnetwork_local, self.qnetwork_target
+        if batch is None:
+            if self._sampler is None or self._sampler.ring is not self.memory:
+                self._sampler = ReplaySampler(self.memory, B, seed=self.key_seed)
+            batch = self._sampler.sample()
+        states, actions, rewards, next_states, dones, valid = batch
+        if int(states.shape[0]) != B or int(next_states.shape[0]) != B:
+            raise ValueError(f"batch= holds {int(states.shape[0])} states; the learner's batch_size is {B}")
+        st = self._prepare()
+        step = self.steps_done
+        # 1: the effective noisy weights of the three network calls
+        f = st.noise_fwd
+        f.draw = step & 0xFFFFFFFFFFFFFFFF
+        for k in range(N_CALLS * N_NOISE):
+            eps = None if noise is None else noise[k]
+            if eps is not None and (eps.dtype != torch.float32 or eps.device != dev or not eps.is_contiguous() or eps.numel() != f.jobs[k].count):
+                raise ValueError(f"noise[{k}] must be a contiguous float32 tensor of {f.jobs[k].count} elements on {dev}")
+            f.jobs[k].eps_in = None if eps is None else eps.data_ptr()
+        N_.launch("sgw_noisy_weights", f, dev)
+        # 2: the three forwards; the third keeps h (its workspace) and its taus
+        for c, (net, x) in enumerate(((local, next_states), (target, next_states), (local, states))):
+            _, flat, _, res = net._check_call(x, self.n_quantiles, None if taus is None else taus[c], st.outs[c])
+            key = {"seed": self.key_seed, "epoch": c, "turn": step & 0xFFFFFFFF, "num_envs": B}
+            net._launch_forward(flat, self._weights(net, st.eff[c]), res, None if taus is None else taus[c], key)
+        # 3: the loss and its gradient at q_expected
+        q = st.outs
+        iqn_loss_terms(q[2].quantiles, q[2].taus, q[0].quantiles, q[1].quantiles, actions, rewards, dones, valid, self.GAMMA ** self.n_step, out=st.loss)
+        # 4: the backward into the parameters' gradients, then the sigmas'
+        d = st.bwd
+        flat = states.reshape(B, -1)
+        d.states, d.state_stride = flat.data_ptr(), int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), flat.shape[1])
+        N_.launch("sgw_iqn_backward", d, dev)
+        N_.launch("sgw_noisy_weights", st.noise_bwd, dev)
+        # 5: clipping, Adam and the soft update
+        self.optimizer.step()
+        self.steps_done += 1
+        self._loss32.copy_(st.loss.loss)
+        return self._loss32
