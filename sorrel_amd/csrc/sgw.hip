@@ -125,6 +125,54 @@ constexpr int kEventPool = 4096;
 
 #include "plan.h"
 
+// the agent keys the host can see (rows without idx): agent0 .. agent0 + (n - 1) / num_envs
+int keyed_agents_check(const char* who, int32_t agent0, int64_t n, int64_t num_envs) {
+    const int64_t last = (int64_t)agent0 + (n > 0 ? (n - 1) / num_envs : 0);
+    if (agent0 < 0 || last >= SGW_MAX_AGENTS)
+        return fail(SGW_EINVAL, "%s: rows are keyed by agents %d .. %lld, outside [0, %d)", who, agent0, (long long)last, SGW_MAX_AGENTS);
+    return SGW_OK;
+}
+
+// the network of a descriptor: sgw_iqn_forward_desc and sgw_iqn_backward_desc name its fields alike, so one check and one fill serve both
+int iqn_sizes(const char* who, int64_t n, int n_bits, int32_t D, int32_t L, int32_t N, int32_t A) {
+    if (n < 0 || (n >> n_bits)) return fail(SGW_EINVAL, "%s: n = %lld outside [0, 2^%d)", who, (long long)n, n_bits);
+    if (D < 1) return fail(SGW_EINVAL, "%s: in_features = %d", who, D);
+    if (L < 1 || L > kFwdMaxL) return fail(SGW_EINVAL, "%s: layer_size = %d outside [1, %d]", who, L, kFwdMaxL);
+    if (N < 1 || N > kFwdM) return fail(SGW_EINVAL, "%s: num_quantiles = %d outside [1, %d]", who, N, kFwdM);
+    if (A < 1 || A > SGW_IQN_MAX_ACTIONS) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, A, SGW_IQN_MAX_ACTIONS);
+    return SGW_OK;
+}
+
+// states, the ten weights, the sizes (n below 2^n_bits) and the largest byte offset into the states: 4 n state_stride
+template <class Desc>
+int iqn_network_check(const Desc* d, const char* who, int n_bits) {
+    if (!d->states || !d->w_head || !d->b_head || !d->w_cos || !d->b_cos || !d->w_ff || !d->b_ff || !d->w_adv || !d->b_adv || !d->w_val || !d->b_val)
+        return fail(SGW_EINVAL, "%s: states and the ten weight pointers must not be NULL", who);
+    if (int rc = iqn_sizes(who, d->n, n_bits, d->in_features, d->layer_size, d->num_quantiles, d->num_actions)) return rc;
+    if (d->n_cos != SGW_IQN_N_COS) return fail(SGW_EINVAL, "%s: n_cos = %d: only %d is built", who, d->n_cos, SGW_IQN_N_COS);
+    if (d->state_type != SGW_IQN_STATE_F32 && d->state_type != SGW_IQN_STATE_U8) return fail(SGW_EINVAL, "%s: unknown state_type %d", who, d->state_type);
+    if (d->state_stride < d->in_features) return fail(SGW_EINVAL, "%s: state_stride = %lld is smaller than in_features = %d", who, (long long)d->state_stride, d->in_features);
+    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
+    if (d->state_type == SGW_IQN_STATE_F32 && misaligned(3, {d->states})) return fail(SGW_EINVAL, "%s: states is not aligned to its element type", who);
+    if (misaligned(3, {d->w_head, d->b_head, d->w_cos, d->b_cos, d->w_ff, d->b_ff, d->w_adv, d->b_adv, d->w_val, d->b_val}))
+        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (a weight)", who);
+    if (d->n > INT64_MAX / 8 / d->state_stride)
+        return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->state_stride);
+    return SGW_OK;
+}
+
+// what both directions' kernels read of IqnFwdParams (the caller adds h, and the forward its key and its outputs)
+template <class Desc>
+void iqn_network_fill(IqnFwdParams& p, const Desc* d) {
+    p.states = d->states;
+    p.w_head = d->w_head; p.b_head = d->b_head; p.w_cos = d->w_cos; p.b_cos = d->b_cos; p.w_ff = d->w_ff; p.b_ff = d->b_ff;
+    p.w_adv = d->w_adv; p.b_adv = d->b_adv; p.w_val = d->w_val; p.b_val = d->b_val; p.taus = d->taus;
+    p.n = d->n; p.stride = d->state_stride; p.num_envs = 1;
+    p.D = d->in_features; p.L = d->layer_size; p.N = d->num_quantiles; p.A = d->num_actions; p.u8 = d->state_type == SGW_IQN_STATE_U8;
+    p.R = kFwdM / d->num_quantiles;
+    p.q_tiles = ceil_div(d->n, p.R);
+}
+
 }  // namespace
 
 struct sgw_engine : Plan {   // the plan (plan.h: what make_plan decided) + the run-time state below, which the planner never writes
@@ -1391,11 +1439,8 @@ static int policy_launch(const sgw_policy_desc* d, const TurnState* ts, const ch
     if (d->mode != SGW_POLICY_PROBS && d->mode != SGW_POLICY_LOGITS) return fail(SGW_EINVAL, "%s: unknown mode %d", who, d->mode);
     if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
     if (d->epoch >= (1u << 28)) return fail(SGW_EINVAL, "%s: epoch must be < 2^28", who);
-    if (!d->idx) {      // the agent keys the host can see: agent0 .. agent0 + (n - 1) / num_envs
-        const int64_t last = (int64_t)d->agent0 + (d->n > 0 ? (d->n - 1) / d->num_envs : 0);
-        if (d->agent0 < 0 || last >= SGW_MAX_AGENTS)
-            return fail(SGW_EINVAL, "%s: rows are keyed by agents %d .. %lld, outside [0, %d)", who, d->agent0, (long long)last, SGW_MAX_AGENTS);
-    }
+    if (!d->idx)
+        if (int rc = keyed_agents_check(who, d->agent0, d->n, d->num_envs)) return rc;
     const bool f64 = d->dist_type == SGW_POLICY_F64;
     const int64_t esz = f64 ? 8 : 4;
     if (misaligned(float_mask(d->dist_type), {d->dist})) return fail(SGW_EINVAL, "%s: dist is not aligned to its element type", who);
@@ -1547,48 +1592,31 @@ int64_t sgw_iqn_forward_workspace_bytes(int64_t n, int32_t layer_size) {
 }
 
 static int iqn_forward_launch(const sgw_iqn_forward_desc* d, const TurnState* ts, const char* who, void* stream) {
-    if (!d->states || !d->w_head || !d->b_head || !d->w_cos || !d->b_cos || !d->w_ff || !d->b_ff || !d->w_adv || !d->b_adv || !d->w_val || !d->b_val)
-        return fail(SGW_EINVAL, "%s: states and the ten weight pointers must not be NULL", who);
+    if (int rc = iqn_network_check(d, who, 63)) return rc;
     if (!d->out_qvalues && !d->out_quantiles) return fail(SGW_EINVAL, "%s: one of out_qvalues and out_quantiles must be given", who);
-    if (d->n < 0) return fail(SGW_EINVAL, "%s: n = %lld", who, (long long)d->n);
-    if (d->in_features < 1) return fail(SGW_EINVAL, "%s: in_features = %d", who, d->in_features);
-    if (d->layer_size < 1 || d->layer_size > kFwdMaxL) return fail(SGW_EINVAL, "%s: layer_size = %d outside [1, %d]", who, d->layer_size, kFwdMaxL);
-    if (d->num_quantiles < 1 || d->num_quantiles > kFwdM) return fail(SGW_EINVAL, "%s: num_quantiles = %d outside [1, %d]", who, d->num_quantiles, kFwdM);
-    if (d->num_actions < 1 || d->num_actions > SGW_IQN_MAX_ACTIONS) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, d->num_actions, SGW_IQN_MAX_ACTIONS);
-    if (d->n_cos != SGW_IQN_N_COS) return fail(SGW_EINVAL, "%s: n_cos = %d: only %d is built", who, d->n_cos, SGW_IQN_N_COS);
-    if (d->state_type != SGW_IQN_STATE_F32 && d->state_type != SGW_IQN_STATE_U8) return fail(SGW_EINVAL, "%s: unknown state_type %d", who, d->state_type);
-    if (d->state_stride < d->in_features) return fail(SGW_EINVAL, "%s: state_stride = %lld is smaller than in_features = %d", who, (long long)d->state_stride, d->in_features);
-    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
     if (!d->taus) {                           // the draw's key
         if (d->num_envs < 1) return fail(SGW_EINVAL, "%s: num_envs = %lld", who, (long long)d->num_envs);
         if (d->epoch >= (1u << 28)) return fail(SGW_EINVAL, "%s: epoch must be < 2^28", who);
-        if (!d->idx) {
-            const int64_t last = (int64_t)d->agent0 + (d->n > 0 ? (d->n - 1) / d->num_envs : 0);
-            if (d->agent0 < 0 || last >= SGW_MAX_AGENTS)
-                return fail(SGW_EINVAL, "%s: rows are keyed by agents %d .. %lld, outside [0, %d)", who, d->agent0, (long long)last, SGW_MAX_AGENTS);
-        }
+        if (!d->idx)
+            if (int rc = keyed_agents_check(who, d->agent0, d->n, d->num_envs)) return rc;
     }
-    if (d->state_type == SGW_IQN_STATE_F32 && misaligned(3, {d->states})) return fail(SGW_EINVAL, "%s: states is not aligned to its element type", who);
-    if (misaligned(3, {d->w_head, d->b_head, d->w_cos, d->b_cos, d->w_ff, d->b_ff, d->w_adv, d->b_adv, d->w_val, d->b_val, d->taus, d->out_qvalues,
-                       d->out_quantiles, d->out_taus, d->out_cos, d->workspace}))
-        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (a weight, taus, an output or the workspace)", who);
+    if (misaligned(3, {d->taus, d->out_qvalues, d->out_quantiles, d->out_taus, d->out_cos, d->workspace}))
+        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (taus, an output or the workspace)", who);
     if (misaligned(7, {d->idx})) return fail(SGW_EINVAL, "%s: misaligned int64 pointer (idx)", who);
-    // the largest byte offsets: 4 n state_stride (states), 4 n N max(64, A) (out_cos, out_quantiles), 4 n L (the workspace)
-    if (d->n > INT64_MAX / 8 / d->state_stride || d->n > INT64_MAX / 8 / ((int64_t)kFwdM * kFwdMaxL))
-        return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->state_stride);
+    // the other large byte offsets: 4 n N max(64, A) (out_cos, out_quantiles), 4 n L (the workspace)
+    if (d->n > INT64_MAX / 8 / ((int64_t)kFwdM * kFwdMaxL))
+        return fail(SGW_EINVAL, "%s: n = %lld rows do not fit 64-bit offsets", who, (long long)d->n);
     if (int rc = workspace_short(who, d->workspace, d->workspace_bytes, d->n * d->layer_size * (int64_t)sizeof(float))) return rc;
     if (d->n == 0) return SGW_OK;
     IqnFwdParams p{};
-    p.states = d->states;
-    p.w_head = d->w_head; p.b_head = d->b_head; p.w_cos = d->w_cos; p.b_cos = d->b_cos; p.w_ff = d->w_ff; p.b_ff = d->b_ff;
-    p.w_adv = d->w_adv; p.b_adv = d->b_adv; p.w_val = d->w_val; p.b_val = d->b_val; p.taus = d->taus; p.idx = d->idx;
+    iqn_network_fill(p, d);
+    p.idx = d->idx;
     p.out_q = d->out_qvalues; p.out_quant = d->out_quantiles; p.out_taus = d->out_taus; p.out_cos = d->out_cos;
     p.h = static_cast<float*>(d->workspace);
     p.ts = ts;
-    p.n = d->n; p.stride = d->state_stride; p.num_envs = d->taus ? 1 : d->num_envs;
-    p.D = d->in_features; p.L = d->layer_size; p.N = d->num_quantiles; p.A = d->num_actions; p.u8 = d->state_type == SGW_IQN_STATE_U8;
-    p.agent0 = d->agent0; p.R = kFwdM / d->num_quantiles;
-    p.head_tiles = ceil_div(d->n, kFwdM); p.q_tiles = ceil_div(d->n, p.R);
+    if (!d->taus) p.num_envs = d->num_envs;
+    p.agent0 = d->agent0;
+    p.head_tiles = ceil_div(d->n, kFwdM);
     p.seed_lo = (uint32_t)d->seed; p.seed_hi = (uint32_t)(d->seed >> 32); p.first_env = (uint32_t)d->first_env;
     p.epoch = d->epoch; p.turn = d->turn;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1620,52 +1648,26 @@ int sgw_turn_iqn_forward(sgw_engine* e, int32_t agent, const sgw_iqn_forward_des
 // floats of workspace per quantile row (z, y, dy, de, c, dO) and per state (dhp)
 static int64_t iqn_backward_floats(int64_t n, int64_t L, int64_t N, int64_t A) { return n * N * (4 * L + SGW_IQN_N_COS + A + 1) + n * L; }
 
-static int iqn_backward_sizes(const char* who, int64_t n, int32_t D, int32_t L, int32_t N, int32_t A) {
-    if (n < 0 || n >= ((int64_t)1 << 40)) return fail(SGW_EINVAL, "%s: n = %lld outside [0, 2^40)", who, (long long)n);
-    if (D < 1) return fail(SGW_EINVAL, "%s: in_features = %d", who, D);
-    if (L < 1 || L > kFwdMaxL) return fail(SGW_EINVAL, "%s: layer_size = %d outside [1, %d]", who, L, kFwdMaxL);
-    if (N < 1 || N > kFwdM) return fail(SGW_EINVAL, "%s: num_quantiles = %d outside [1, %d]", who, N, kFwdM);
-    if (A < 1 || A > SGW_IQN_MAX_ACTIONS) return fail(SGW_EINVAL, "%s: num_actions = %d outside [1, %d]", who, A, SGW_IQN_MAX_ACTIONS);
-    return SGW_OK;
-}
-
 int64_t sgw_iqn_backward_workspace_bytes(int64_t n, int32_t in_features, int32_t layer_size, int32_t num_quantiles, int32_t num_actions) {
-    if (int rc = iqn_backward_sizes("sgw_iqn_backward_workspace_bytes", n, in_features, layer_size, num_quantiles, num_actions)) return rc;
+    if (int rc = iqn_sizes("sgw_iqn_backward_workspace_bytes", n, 40, in_features, layer_size, num_quantiles, num_actions)) return rc;
     return iqn_backward_floats(n, layer_size, num_quantiles, num_actions) * (int64_t)sizeof(float);     // (< 2^40 * 2^17 * 4)
 }
 
 int sgw_iqn_backward(const sgw_iqn_backward_desc* d, void* stream) {
     const char* who = "sgw_iqn_backward";
     if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
-    if (!d->states || !d->w_head || !d->b_head || !d->w_cos || !d->b_cos || !d->w_ff || !d->b_ff || !d->w_adv || !d->b_adv || !d->w_val || !d->b_val)
-        return fail(SGW_EINVAL, "%s: states and the ten weight pointers must not be NULL", who);
+    if (int rc = iqn_network_check(d, who, 40)) return rc;        // (n < 2^40: the workspace's byte offsets stay below 2^59)
     if (!d->taus || !d->h || !d->grad_quantiles) return fail(SGW_EINVAL, "%s: taus, h and grad_quantiles must not be NULL", who);
-    if (int rc = iqn_backward_sizes(who, d->n, d->in_features, d->layer_size, d->num_quantiles, d->num_actions)) return rc;
-    if (d->n_cos != SGW_IQN_N_COS) return fail(SGW_EINVAL, "%s: n_cos = %d: only %d is built", who, d->n_cos, SGW_IQN_N_COS);
-    if (d->state_type != SGW_IQN_STATE_F32 && d->state_type != SGW_IQN_STATE_U8) return fail(SGW_EINVAL, "%s: unknown state_type %d", who, d->state_type);
-    if (d->state_stride < d->in_features) return fail(SGW_EINVAL, "%s: state_stride = %lld is smaller than in_features = %d", who, (long long)d->state_stride, d->in_features);
-    if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
-    if (d->state_type == SGW_IQN_STATE_F32 && misaligned(3, {d->states})) return fail(SGW_EINVAL, "%s: states is not aligned to its element type", who);
-    if (misaligned(3, {d->w_head, d->b_head, d->w_cos, d->b_cos, d->w_ff, d->b_ff, d->w_adv, d->b_adv, d->w_val, d->b_val, d->taus, d->h, d->grad_quantiles,
-                       d->out_w_head, d->out_b_head, d->out_w_cos, d->out_b_cos, d->out_w_ff, d->out_b_ff, d->out_w_adv, d->out_b_adv, d->out_w_val,
-                       d->out_b_val, d->out_grad_h, d->workspace}))
-        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (a weight, taus, h, grad_quantiles, an output or the workspace)", who);
-    // the largest byte offsets: 4 n state_stride (states); the workspace's (n < 2^40: below 2^59)
-    if (d->n > INT64_MAX / 8 / d->state_stride)
-        return fail(SGW_EINVAL, "%s: n = %lld rows of stride %lld do not fit 64-bit offsets", who, (long long)d->n, (long long)d->state_stride);
+    if (misaligned(3, {d->taus, d->h, d->grad_quantiles, d->out_w_head, d->out_b_head, d->out_w_cos, d->out_b_cos, d->out_w_ff, d->out_b_ff, d->out_w_adv,
+                       d->out_b_adv, d->out_w_val, d->out_b_val, d->out_grad_h, d->workspace}))
+        return fail(SGW_EINVAL, "%s: misaligned float32 pointer (taus, h, grad_quantiles, an output or the workspace)", who);
     const int64_t n = d->n, L = d->layer_size, N = d->num_quantiles, A = d->num_actions, D = d->in_features, M = n * N;
     if (int rc = workspace_short(who, d->workspace, d->workspace_bytes, iqn_backward_floats(n, L, N, A) * (int64_t)sizeof(float))) return rc;
     if (n == 0) return SGW_OK;
     IqnBwdParams b{};
     IqnFwdParams& p = b.f;
-    p.states = d->states;
-    p.w_head = d->w_head; p.b_head = d->b_head; p.w_cos = d->w_cos; p.b_cos = d->b_cos; p.w_ff = d->w_ff; p.b_ff = d->b_ff;
-    p.w_adv = d->w_adv; p.b_adv = d->b_adv; p.w_val = d->w_val; p.b_val = d->b_val; p.taus = d->taus;
+    iqn_network_fill(p, d);
     p.h = const_cast<float*>(d->h);           // (read only here)
-    p.n = n; p.stride = d->state_stride; p.num_envs = 1;
-    p.D = (int32_t)D; p.L = (int32_t)L; p.N = (int32_t)N; p.A = (int32_t)A; p.u8 = d->state_type == SGW_IQN_STATE_U8;
-    p.R = kFwdM / (int32_t)N;
-    p.q_tiles = ceil_div(n, p.R);
     b.grad = d->grad_quantiles;
     float* w = static_cast<float*>(d->workspace);
     b.z = w; b.y = b.z + M * L; b.dy = b.y + M * L; b.de = b.dy + M * L; b.c = b.de + M * L; b.dO = b.c + M * SGW_IQN_N_COS; b.dhp = b.dO + M * (A + 1);

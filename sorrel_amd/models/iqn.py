@@ -1,7 +1,8 @@
 """IQN's Q-network (``sorrel/models/pytorch/iqn.py:51-167`` and ``layers.py``'s ``NoisyLinear``): the modules, with the reference's
 parameter and buffer names and shapes so that its ``state_dict`` loads, and the forward pass on the device.
 
-* ``IQN.forward(input, n_tau)`` is the reference's sequence of torch ops: it supports autograd, runs on the CPU and is the baseline.
+* ``IQN.forward(input, n_tau)`` is the reference's sequence of torch ops: it supports autograd, runs on the CPU and is the baseline.  The
+  ops are written once, in ``IQN.forward_flat``; every entry point that gets CPU tensors, the learner's CPU step included, calls it.
 * ``IQN.quantiles`` / ``IQN.get_qvalues`` run ``sgw_iqn_forward`` (``sorrel_amd/csrc/iqn_forward.h``: two launches, nothing of size
   ``[B N, L]`` through memory) for device tensors, without autograd: acting, and the two ``next_states`` calls of a learner's step.  The
   taus are given, or drawn KEYED by (seed, env, epoch, turn, agent, quantile) so that a recorded turn draws fresh ones on every replay.
@@ -24,6 +25,24 @@ from sorrel_amd import _native as N_
 from sorrel_amd.models.base_model import BaseModel
 
 N_COS, MAX_LAYER, MAX_QUANTILES, MAX_ACTIONS = N_.IQN_N_COS, N_.IQN_MAX_LAYER, N_.IQN_MAX_QUANTILES, N_.IQN_MAX_ACTIONS    # (the header's)
+# the ten weight fields of SgwIqnForwardDesc and SgwIqnBackwardDesc (the latter's gradients: "out_" + name), in the order of IQN.weight_list
+WEIGHT_FIELDS = ("w_head", "b_head", "w_cos", "b_cos", "w_ff", "b_ff", "w_adv", "b_adv", "w_val", "b_val")
+
+
+def fill_network_desc(d, flat=None, ws=None, sizes=None):
+    """What ``SgwIqnForwardDesc`` and ``SgwIqnBackwardDesc`` share, over checked arguments: the states of a call (``flat`` ``[B, D]``), the
+    ten weights (``ws``) and the network's ``sizes`` ``(L, N, A)``; a part that is None is left as it is."""
+    if flat is not None:
+        B, D = flat.shape
+        d.states, d.n, d.in_features = flat.data_ptr(), B, D
+        d.state_stride = int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), D)      # (one row: its stride is arbitrary)
+        d.state_type = N_.IQN_STATE_U8 if flat.dtype == torch.uint8 else N_.IQN_STATE_F32
+    if ws is not None:
+        for name, w in zip(WEIGHT_FIELDS, ws):
+            setattr(d, name, w.data_ptr())
+    if sizes is not None:
+        d.layer_size, d.num_quantiles, d.num_actions = sizes
+        d.n_cos = N_COS
 
 
 class NoisyLinear(nn.Linear):
@@ -44,16 +63,22 @@ class NoisyLinear(nn.Linear):
         self.weight.data.uniform_(-std, std)
         self.bias.data.uniform_(-std, std)
 
-    def effective(self, resample: bool = True):
-        """The (weight, bias) this layer applies now: in training mode new noise is drawn first (``resample``), as ``forward`` does."""
-        if not self.training:
+    def effective(self, resample: bool = True, eps=None, noisy: Optional[bool] = None):
+        """The (weight, bias) this layer applies now: in training mode (``noisy`` overrides it) ``weight + sigma * epsilon`` after new
+        noise is drawn (``resample``, as ``forward`` does) or an ``eps`` pair (weight, bias) is copied into the epsilon buffers; else the
+        mean weights."""
+        if not (self.training if noisy is None else noisy):
             return self.weight, self.bias
-        if resample:
+        if eps is not None:
+            self.epsilon_weight.copy_(eps[0])
+        elif resample:
             self.epsilon_weight.normal_()
         weight = self.weight + self.sigma_weight * self.epsilon_weight
         bias = None
         if self.bias is not None:
-            if resample:
+            if eps is not None:
+                self.epsilon_bias.copy_(eps[1])
+            elif resample:
                 self.epsilon_bias.normal_()
             bias = self.bias + self.sigma_bias * self.epsilon_bias
         return weight, bias
@@ -107,26 +132,35 @@ class IQN(nn.Module):
         self.to(device)
 
     # ------------------------------------------------------------------------------------------------ the torch-op path (the baseline)
-    def calc_cos(self, batch_size: int, n_tau: int = 8):
-        taus = torch.rand(batch_size, n_tau).unsqueeze(-1).to(self.pis.device)
+    def calc_cos(self, batch_size: int, n_tau: int = 8, taus=None):
+        if taus is None:
+            taus = torch.rand(batch_size, n_tau).unsqueeze(-1).to(self.pis.device)
+        else:
+            taus = taus.reshape(batch_size, n_tau, 1)
         cos = torch.cos(taus * self.pis)
         assert cos.shape == (batch_size, n_tau, self.n_cos), "cos shape is incorrect"
         return cos, taus
 
-    def forward(self, input: torch.Tensor, n_tau: int = 8):
-        batch_size = input.size()[0]
-        r_in = input.view(batch_size, -1)
-        x = torch.relu(self.head1(r_in))
-        cos, taus = self.calc_cos(batch_size, n_tau)
+    def forward_flat(self, flat: torch.Tensor, n_tau: int, taus=None, noise: Optional[bool] = None, eps=None):
+        """The network's torch ops over flat states ``[B, D]`` (not cast): ``(quantiles [B, N, A], taus [B, N, 1])``.  The taus are as
+        given, or drawn first.  The noisy layers follow ``training`` (``noise`` None), apply noise whatever it says (True: fresh, or the
+        six ``eps`` tensors, ``ff_1``, ``advantage``, ``value``, weight before bias) or use the mean weights (False)."""
+        batch_size = flat.shape[0]
+        eps = [None] * 3 if eps is None else [eps[0:2], eps[2:4], eps[4:6]]
+        x = torch.relu(self.head1(flat))
+        cos, taus = self.calc_cos(batch_size, n_tau) if taus is None else self.calc_cos(batch_size, n_tau, taus)      # (drawn: the reference's call)
         cos = cos.view(batch_size * n_tau, self.n_cos)
         cos = torch.relu(self.cos_embedding(cos))
         cos_x = cos.view(batch_size, n_tau, self.cos_layer_out)
         x = (x.unsqueeze(1) * cos_x).view(batch_size * n_tau, self.cos_layer_out)
-        x = torch.relu(self.ff_1(x))
-        advantage = self.advantage(x)
-        value = self.value(x)
+        x = torch.relu(F.linear(x, *self.ff_1.effective(eps=eps[0], noisy=noise)))
+        advantage = F.linear(x, *self.advantage.effective(eps=eps[1], noisy=noise))
+        value = F.linear(x, *self.value.effective(eps=eps[2], noisy=noise))
         out = value + advantage - advantage.mean(dim=1, keepdim=True)
         return out.view(batch_size, n_tau, self.action_space), taus
+
+    def forward(self, input: torch.Tensor, n_tau: int = 8):
+        return self.forward_flat(input.view(input.size()[0], -1), n_tau)
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
@@ -134,20 +168,25 @@ class IQN(nn.Module):
         return self
 
     # ------------------------------------------------------------------------------------------------ the device path
+    def weight_list(self, noisy="mean", resample: bool = True):
+        """The ten tensors in the order of ``WEIGHT_FIELDS``, as they are (not detached).  The noisy layers' six are the mean parameters
+        (``"mean"``), what the layers apply now (``"effective"``: ``NoisyLinear.effective(resample)``) or six tensors of the caller's."""
+        layers = (self.ff_1, self.advantage, self.value)
+        if isinstance(noisy, str):
+            noisy = [t for layer in layers for t in (layer.effective(resample) if noisy == "effective" else (layer.weight, layer.bias))]
+        return [self.head1.weight, self.head1.bias, self.cos_embedding.weight, self.cos_embedding.bias, *noisy]
+
     def effective_weights(self, out: Optional[IQNOutput] = None, resample: bool = True):
         """The ten tensors ``sgw_iqn_forward`` takes, detached: in eval mode the parameters themselves; in training mode
         ``weight + sigma * epsilon`` of the three noisy layers with fresh noise (``resample``), composed into ``out``'s storage if given."""
         with torch.no_grad():
-            ws = [self.head1.weight, self.head1.bias, self.cos_embedding.weight, self.cos_embedding.bias]
-            noisy = [self.ff_1.effective(resample), self.advantage.effective(resample), self.value.effective(resample)]
+            ws = self.weight_list("effective", resample)
             if self.training and out is not None:
                 if out._weights is None:
-                    out._weights = [torch.empty_like(t) for pair in noisy for t in pair]
-                for dst, src in zip(out._weights, [t for pair in noisy for t in pair]):
+                    out._weights = [torch.empty_like(t) for t in ws[4:]]
+                for dst, src in zip(out._weights, ws[4:]):
                     dst.copy_(src)
-                ws += out._weights
-            else:
-                ws += [t for pair in noisy for t in pair]
+                ws[4:] = out._weights
             return [w.detach() for w in ws]
 
     def _check_states(self, states):
@@ -177,7 +216,14 @@ class IQN(nn.Module):
         B, flat, N, res = self._check_call(states, n_tau, taus, out, cos)
         dev = flat.device
         if dev.type != "cuda":
-            return self._quantiles_by_torch(flat, N, taus, res)
+            with torch.no_grad():
+                q, t = self.forward_flat(flat.float(), N, taus)
+                res.quantiles.copy_(q)
+                res.taus.copy_(t)
+                res.qvalues.copy_(q.mean(dim=1))
+                if res.cos is not None:
+                    res.cos.copy_(self.calc_cos(B, N, t)[0])
+            return res
         ws = self.effective_weights(res if out is not None else None)
         return self._launch_forward(flat, ws, res, taus, key, cos, engine, agent)
 
@@ -220,15 +266,11 @@ class IQN(nn.Module):
         if B == 0:
             return res
         d = N_.SgwIqnForwardDesc()
-        d.states = flat.data_ptr()
-        (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
+        fill_network_desc(d, flat, ws, (L, N, A))
         d.out_qvalues, d.out_quantiles, d.out_taus = res.qvalues.data_ptr(), res.quantiles.data_ptr(), res.taus.data_ptr()
         if res.cos is not None and cos:
             d.out_cos = res.cos.data_ptr()
         d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
-        d.n, d.state_stride = B, int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), flat.shape[1])
-        d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = flat.shape[1], L, N, A, N_COS
-        d.state_type = N_.IQN_STATE_U8 if flat.dtype == torch.uint8 else N_.IQN_STATE_F32
         keep = None
         if taus is not None:
             d.taus = taus.data_ptr()
@@ -252,24 +294,6 @@ class IQN(nn.Module):
             N_.launch("sgw_iqn_forward", d, dev)
         return res
 
-    def _quantiles_by_torch(self, flat, N, taus, res):
-        with torch.no_grad():
-            B = flat.shape[0]
-            x = torch.relu(self.head1(flat.float()))
-            t = (torch.rand(B, N, device=flat.device) if taus is None else taus).reshape(B, N, 1)
-            c = torch.cos(t * self.pis)
-            e = torch.relu(self.cos_embedding(c.view(B * N, self.n_cos))).view(B, N, self.layer_size)
-            z = (x.unsqueeze(1) * e).view(B * N, self.layer_size)
-            y = torch.relu(self.ff_1(z))
-            adv, val = self.advantage(y), self.value(y)
-            q = (val + adv - adv.mean(dim=1, keepdim=True)).view(B, N, self.action_space)
-            res.quantiles.copy_(q)
-            res.taus.copy_(t)
-            res.qvalues.copy_(q.mean(dim=1))
-            if res.cos is not None:
-                res.cos.copy_(c)
-        return res
-
     # ------------------------------------------------------------------------------------------------ the device path with autograd
     def forward_fused(self, states, n_tau: Optional[int] = None, *, taus=None, key=None, out: Optional[IQNOutput] = None):
         """``forward``'s results -- ``(quantiles [B, N, A], taus [B, N, 1])`` -- WITH autograd and without torch's network ops: on a HIP
@@ -281,25 +305,9 @@ class IQN(nn.Module):
         given taus."""
         B, flat, N, res = self._check_call(states, n_tau, taus, out)
         if flat.device.type != "cuda":
-            return self._forward_by_torch(flat, N, taus)
-        ws = [self.head1.weight, self.head1.bias, self.cos_embedding.weight, self.cos_embedding.bias]
-        for layer in (self.ff_1, self.advantage, self.value):
-            ws += list(layer.effective())
-        quantiles = _FusedQuantiles.apply(self, flat, res, taus, key, *ws)
+            return self.forward_flat(flat.float(), N, taus)
+        quantiles = _FusedQuantiles.apply(self, flat, res, taus, key, *self.weight_list("effective"))
         return quantiles, res.taus
-
-    def _forward_by_torch(self, flat, N, taus):
-        """``forward`` on flat states with the taus given (or drawn as ``calc_cos`` draws them)."""
-        B = flat.shape[0]
-        t = (torch.rand(B, N).to(self.pis.device) if taus is None else taus).reshape(B, N, 1)
-        x = torch.relu(self.head1(flat.float()))
-        c = torch.cos(t * self.pis).view(B * N, self.n_cos)
-        e = torch.relu(self.cos_embedding(c)).view(B, N, self.cos_layer_out)
-        z = (x.unsqueeze(1) * e).view(B * N, self.cos_layer_out)
-        y = torch.relu(self.ff_1(z))
-        adv, val = self.advantage(y), self.value(y)
-        out = val + adv - adv.mean(dim=1, keepdim=True)
-        return out.view(B, N, self.action_space), t
 
     def get_qvalues(self, inputs, n_tau: Optional[int] = None, **kwargs):
         """The mean of the quantiles, float32 ``[B, A]`` (``iqn.py:164-167``).  Tensors that require no kernel -- the CPU, or a call under
@@ -338,16 +346,12 @@ class _FusedQuantiles(torch.autograd.Function):
             D = int(flat.shape[1])
             space = N_.workspace(int(N_.load().sgw_iqn_backward_workspace_bytes(B, D, L, N, A)), dev)
             d = N_.SgwIqnBackwardDesc()
-            d.states = flat.data_ptr()
-            (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
+            fill_network_desc(d, flat, ws, (L, N, A))
             d.taus, d.h, d.grad_quantiles = res.taus.data_ptr(), res._workspace.data_ptr(), grad.data_ptr()
-            for name, g in zip(("w_head", "b_head", "w_cos", "b_cos", "w_ff", "b_ff", "w_adv", "b_adv", "w_val", "b_val"), grads):
+            for name, g in zip(WEIGHT_FIELDS, grads):
                 if g is not None:
                     setattr(d, "out_" + name, g.data_ptr())
             d.workspace, d.workspace_bytes = space.data_ptr(), space.numel() * 8
-            d.n, d.state_stride = B, int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), D)
-            d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = D, L, N, A, N_COS
-            d.state_type = N_.IQN_STATE_U8 if flat.dtype == torch.uint8 else N_.IQN_STATE_F32
             N_.launch("sgw_iqn_backward", d, dev)
         return (None, None, None, None, None, *grads)
 
@@ -373,19 +377,31 @@ class IQNActor(BaseModel):
         return self
 
     def take_action(self, state):
-        B = int(state.shape[0])
-        if state.device.type != "cuda":
-            return self.net.get_qvalues(state.reshape(B, -1).float()).detach()
-        if self._out is None or self._out.quantiles.shape[0] != B or self._out.quantiles.device != state.device:
-            self._out = IQNOutput(B, self.net.n_quantiles, self.net.action_space, self.net.layer_size, state.device)
-        env = self._env
-        if env is None:
-            return self.net.quantiles(state, out=self._out).qvalues
+        q, self._out = act_values(self.net, state, self._out, self._env, self._slot, mean=False)
+        return q
+
+
+def act_values(net: IQN, state, out: Optional[IQNOutput], env, slot: int, mean: bool):
+    """The float32 ``[E, A]`` action values of ``state`` without autograd, and the ``IQNOutput`` they live in (``out`` if it fits, else a new
+    one; None on the CPU): what a bound model's ``take_action`` returns and keeps.  ``mean`` takes the mean weights whatever ``training``
+    says; otherwise the network acts as ``quantiles`` does.  The taus are keyed by ``env``'s turn for agent ``slot`` (None: by the network's
+    own count of calls): eagerly the environment's (seed, epoch, turn) go into the call, under ``capture_turn()`` the device reads them."""
+    B = int(state.shape[0])
+    if state.device.type != "cuda":
+        with torch.no_grad():
+            q, _ = net.forward_flat(state.reshape(B, -1).float(), net.n_quantiles, noise=False if mean else None)
+            return q.mean(dim=1), None
+    if out is None or out.quantiles.shape[0] != B or out.quantiles.device != state.device:
+        out = IQNOutput(B, net.n_quantiles, net.action_space, net.layer_size, state.device)
+    _, flat, _, res = net._check_call(state, None, None, out)
+    ws = net.weight_list() if mean else net.effective_weights(res)
+    key = eng = None
+    if env is not None:
         eng = env._ensure_engine()
         if getattr(env, "_mixed", False):
-            eng = env._agent_engine[self._slot]
-        if env._turn_capture:
-            return self.net.quantiles(state, out=self._out, engine=eng, agent=self._slot).qvalues
-        key = {"seed": int(eng.spec.seed), "epoch": int(env.epoch), "turn": int(env.turn), "num_envs": int(eng.num_envs), "agent0": self._slot,
-               "first_env": int(eng.first_env_id)}
-        return self.net.quantiles(state, out=self._out, key=key).qvalues
+            eng = env._agent_engine[slot]
+        if not env._turn_capture:
+            key = {"seed": int(eng.spec.seed), "epoch": int(env.epoch), "turn": int(env.turn), "num_envs": int(eng.num_envs), "agent0": slot,
+                   "first_env": int(eng.first_env_id)}
+            eng = None
+    return net._launch_forward(flat, ws, res, key=key, engine=eng, agent=slot).qvalues, res

@@ -18,12 +18,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from sorrel_amd import _native as N_
 from sorrel_amd.buffers import Buffer, ReplaySampler
 from sorrel_amd.models.base_model import BaseModel
-from sorrel_amd.models.iqn import IQN, N_COS, IQNOutput
+from sorrel_amd.models.iqn import IQN, WEIGHT_FIELDS, IQNOutput, act_values, fill_network_desc
 from sorrel_amd.optim import FusedAdam
 from sorrel_amd.spec import resolve_device
 
@@ -39,38 +38,6 @@ def _noisy_tensors(net: IQN):
         layer = getattr(net, name)
         out += [(layer.weight, layer.sigma_weight), (layer.bias, layer.sigma_bias)]
     return out
-
-
-def _network_torch(net: IQN, flat, n_tau: int, taus=None, eps=None, mean: bool = False):
-    """``IQN.forward``'s lines on flat states: the taus as given or drawn as ``calc_cos`` draws them; the noisy layers with the six ``eps``
-    tensors given, with fresh ``normal_()`` noise (``eps`` None, as ``NoisyLinear.forward`` in training mode), or with the mean weights."""
-    B = flat.shape[0]
-    t = torch.rand(B, n_tau).unsqueeze(-1).to(net.pis.device) if taus is None else taus.reshape(B, n_tau, 1)
-    x = torch.relu(net.head1(flat))
-    cos = torch.cos(t * net.pis).view(B * n_tau, net.n_cos)
-    cos = torch.relu(net.cos_embedding(cos))
-    cos_x = cos.view(B, n_tau, net.cos_layer_out)
-    x = (x.unsqueeze(1) * cos_x).view(B * n_tau, net.cos_layer_out)
-
-    def noisy(k, x):
-        layer = getattr(net, NOISY_LAYERS[k])
-        if mean:
-            return F.linear(x, layer.weight, layer.bias)
-        if eps is None:
-            layer.epsilon_weight.normal_()
-            layer.epsilon_bias.normal_()
-        else:
-            layer.epsilon_weight.copy_(eps[2 * k])
-            layer.epsilon_bias.copy_(eps[2 * k + 1])
-        weight = layer.weight + layer.sigma_weight * layer.epsilon_weight
-        bias = layer.bias + layer.sigma_bias * layer.epsilon_bias
-        return F.linear(x, weight, bias)
-
-    x = torch.relu(noisy(0, x))
-    advantage = noisy(1, x)
-    value = noisy(2, x)
-    out = value + advantage - advantage.mean(dim=1, keepdim=True)
-    return out.view(B, n_tau, net.action_space), t
 
 
 class _DeviceStep:
@@ -114,36 +81,10 @@ class iRainbowModel(BaseModel):
         self._env, self._slot = env, int(slot)
         return self
 
-    def _mean_weights(self, net: IQN):
-        ws = [net.head1.weight, net.head1.bias, net.cos_embedding.weight, net.cos_embedding.bias]
-        for name in NOISY_LAYERS:
-            layer = getattr(net, name)
-            ws += [layer.weight, layer.bias]
-        return [w.detach() for w in ws]
-
     def take_action(self, state):
         """The float32 ``[E, A]`` action values of ``qnetwork_local`` with the mean weights, detached."""
-        net = self.qnetwork_local
-        B = int(state.shape[0])
-        if state.device.type != "cuda":
-            with torch.no_grad():
-                q, _ = _network_torch(net, state.reshape(B, -1).float(), self.n_quantiles, mean=True)
-                return q.mean(dim=1)
-        if self._out is None or self._out.quantiles.shape[0] != B or self._out.quantiles.device != state.device:
-            self._out = IQNOutput(B, net.n_quantiles, net.action_space, net.layer_size, state.device)
-        _, flat, _, res = net._check_call(state, None, None, self._out)
-        ws = self._mean_weights(net)
-        env = self._env
-        if env is None:
-            return net._launch_forward(flat, ws, res).qvalues
-        eng = env._ensure_engine()
-        if getattr(env, "_mixed", False):
-            eng = env._agent_engine[self._slot]
-        if env._turn_capture:
-            return net._launch_forward(flat, ws, res, engine=eng, agent=self._slot).qvalues
-        key = {"seed": int(eng.spec.seed), "epoch": int(env.epoch), "turn": int(env.turn), "num_envs": int(eng.num_envs), "agent0": self._slot,
-               "first_env": int(eng.first_env_id)}
-        return net._launch_forward(flat, ws, res, key=key).qvalues
+        q, self._out = act_values(self.qnetwork_local, state, self._out, self._env, self._slot, mean=True)
+        return q
 
     # ------------------------------------------------------------------------------------------------------------ the epoch hooks
     def start_epoch_action(self, **kwargs) -> None:
@@ -204,9 +145,9 @@ class iRainbowModel(BaseModel):
             tau = [None] * N_CALLS if taus is None else list(taus)
             eps = [None] * N_CALLS if noise is None else [noise[c * N_NOISE:(c + 1) * N_NOISE] for c in range(N_CALLS)]
             B = states.shape[0]
-            q_next_local, _ = _network_torch(local, next_states.view(B, -1), n, tau[0], eps[0])
-            q_next_target, _ = _network_torch(target, next_states.view(B, -1), n, tau[1], eps[1])
-            q_expected, t = _network_torch(local, states.view(B, -1), n, tau[2], eps[2])
+            q_next_local, _ = local.forward_flat(next_states.view(B, -1), n, tau[0], noise=True, eps=eps[0])
+            q_next_target, _ = target.forward_flat(next_states.view(B, -1), n, tau[1], noise=True, eps=eps[1])
+            q_expected, t = local.forward_flat(states.view(B, -1), n, tau[2], noise=True, eps=eps[2])
             loss = _iqn_loss_torch(q_expected, t, q_next_local, q_next_target, actions, rewards, dones, valid, self.GAMMA ** self.n_step)[0]
             loss.backward()
             self.optimizer.step()             # clip_grad_norm_(.., 1), Adam, soft_update(): the reference's lines (optim._adam_step_torch)
@@ -252,25 +193,16 @@ class iRainbowModel(BaseModel):
             job = g.jobs[t]
             job.grad_eff, job.eps_in, job.out_grad_sigma, job.count = w.grad.data_ptr(), st.eps[t].data_ptr(), s.grad.data_ptr(), w.numel()
         st.noise_bwd = g
-        d = N_.SgwIqnBackwardDesc()
-        ws = self._weights(local, st.eff[2])
-        (d.w_head, d.b_head, d.w_cos, d.b_cos, d.w_ff, d.b_ff, d.w_adv, d.b_adv, d.w_val, d.b_val) = (w.data_ptr() for w in ws)
+        d = N_.SgwIqnBackwardDesc()               # (the states of a step go in when it runs)
+        fill_network_desc(d, ws=local.weight_list(st.eff[2]), sizes=(L, Nq, A))
         res = st.outs[2]
         d.taus, d.h, d.grad_quantiles = res.taus.data_ptr(), res._workspace.data_ptr(), st.loss.grad_expected.data_ptr()
-        grads = [local.head1.weight.grad, local.head1.bias.grad, local.cos_embedding.weight.grad, local.cos_embedding.bias.grad]
-        grads += [w.grad for w, _ in _noisy_tensors(local)]
-        (d.out_w_head, d.out_b_head, d.out_w_cos, d.out_b_cos, d.out_w_ff, d.out_b_ff, d.out_w_adv, d.out_b_adv, d.out_w_val, d.out_b_val) = (
-            x.data_ptr() for x in grads)
+        for name, w in zip(WEIGHT_FIELDS, local.weight_list()):
+            setattr(d, "out_" + name, w.grad.data_ptr())
         d.workspace, d.workspace_bytes = st.space.data_ptr(), st.space.numel() * 8
-        d.n, d.in_features, d.layer_size, d.num_quantiles, d.num_actions, d.n_cos = B, D, L, Nq, A, N_COS
-        d.state_type = N_.IQN_STATE_F32
         st.bwd = d
         self._step = st
         return st
-
-    @staticmethod
-    def _weights(net: IQN, eff):
-        return [net.head1.weight.detach(), net.head1.bias.detach(), net.cos_embedding.weight.detach(), net.cos_embedding.bias.detach(), *eff]
 
     def _train_step_device(self, batch, taus, noise):
         from sorrel_amd.losses import iqn_loss_terms
@@ -299,15 +231,13 @@ class iRainbowModel(BaseModel):
         for c, (net, x) in enumerate(((local, next_states), (target, next_states), (local, states))):
             _, flat, _, res = net._check_call(x, self.n_quantiles, None if taus is None else taus[c], st.outs[c])
             key = {"seed": self.key_seed, "epoch": c, "turn": step & 0xFFFFFFFF, "num_envs": B}
-            net._launch_forward(flat, self._weights(net, st.eff[c]), res, None if taus is None else taus[c], key)
+            net._launch_forward(flat, net.weight_list(st.eff[c]), res, None if taus is None else taus[c], key)
         # 3: the loss and its gradient at q_expected
         q = st.outs
         iqn_loss_terms(q[2].quantiles, q[2].taus, q[0].quantiles, q[1].quantiles, actions, rewards, dones, valid, self.GAMMA ** self.n_step, out=st.loss)
         # 4: the backward into the parameters' gradients, then the sigmas'
-        d = st.bwd
-        flat = states.reshape(B, -1)
-        d.states, d.state_stride = flat.data_ptr(), int(flat.stride(0)) if B > 1 else max(int(flat.stride(0)), flat.shape[1])
-        N_.launch("sgw_iqn_backward", d, dev)
+        fill_network_desc(st.bwd, states.reshape(B, -1))
+        N_.launch("sgw_iqn_backward", st.bwd, dev)
         N_.launch("sgw_noisy_weights", st.noise_bwd, dev)
         # 5: clipping, Adam and the soft update
         self.optimizer.step()

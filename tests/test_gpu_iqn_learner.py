@@ -195,6 +195,64 @@ def test_take_action_is_the_mean_weights_forward(built):
     assert torch.equal(q, want)
 
 
+def test_bound_actor_and_learner_act_alike_eagerly_and_in_a_recorded_turn(built):
+    from sorrel_amd.models import IQNActor, PyTorchIQN
+    from tests.gpu_common import make_env
+
+    E, A, T = 2, 2, 2
+
+    def build(learner):
+        made = []
+
+        def factory(input_size, action_space):
+            seed = 100 + len(made)
+            if learner:
+                made.append(PyTorchIQN(input_size, action_space, 33, 0.0, DEV, seed, n_frames=1, n_quantiles=5, batch_size=4, memory_size=8, num_envs=E))
+            else:
+                made.append(IQNActor(input_size, action_space, layer_size=33, n_quantiles=5, seed=seed, memory_size=8, num_envs=E, device=DEV))
+            return made[-1]
+
+        env = make_env(8, 8, A, 2, E, p=0.05, seed=23, model_factory=factory)
+        for a, agent in enumerate(env.agents):
+            agent.model.bind(env, a)
+        return env
+
+    acting, learning = build(False), build(True)
+    for a in range(A):
+        local = learning.agents[a].model.qnetwork_local
+        with torch.no_grad():
+            for name in ("ff_1", "advantage", "value"):
+                getattr(local, name).sigma_weight.fill_(0.5)                       # noise would show
+                getattr(local, name).epsilon_weight.normal_()
+        acting.agents[a].model.net.load_state_dict(local.state_dict())
+        assert local.training and not acting.agents[a].model.net.training
+    # eagerly: both bound to the same environment and slot, so both key their taus alike
+    actor, learner = acting.agents[1].model, learning.agents[1].model
+    learner.bind(acting, 1)
+    x = torch.randn((E, actor.net.head1.in_features), device=DEV)
+    qa, ql = actor.take_action(x).clone(), learner.take_action(x).clone()
+    assert qa.shape == (E, actor.net.action_space) and qa.dtype == torch.float32
+    assert torch.equal(actor._out.taus, learner._out.taus) and torch.equal(qa, ql)
+    learner.bind(learning, 1)
+    # recorded: the same world twice, one played by the actors and one by the learners; the device keys a replayed turn's taus
+    caps = [env.capture_turn(warmup=1, force=True) for env in (acting, learning)]
+    assert caps[0] is not None and caps[1] is not None, (acting.capture_error, learning.capture_error)
+    seen = []
+    for t in range(T):
+        acting.take_turn()
+        learning.take_turn()
+        torch.cuda.synchronize()
+        for a in range(A):
+            oa, ol = acting.agents[a].model._out, learning.agents[a].model._out
+            assert torch.equal(oa.taus, ol.taus) and torch.equal(oa.qvalues, ol.qvalues), (t, a)
+        seen.append(acting.agents[0].model._out.taus.clone())
+        assert torch.equal(acting.actions, learning.actions), t
+    assert caps[0].turns_replayed == T and caps[1].turns_replayed == T and not torch.equal(seen[0], seen[1])
+    assert all(agent.model.qnetwork_local.training for agent in learning.agents)
+    acting.raise_on_status()
+    learning.raise_on_status()
+
+
 def _example(capture):
     from sorrel_amd.examples.treasurehunt import main as TH
 

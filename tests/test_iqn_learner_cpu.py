@@ -16,7 +16,6 @@ CASES = [(LC.tag_of(shape), k) for shape in LC.SHAPES for k in range(LC.STEPS)]
 def eval_loss(model, args):
     """The loss of a batch with the mean weights and the given taus, computed on the CPU from copies of both networks."""
     from sorrel_amd.losses import _iqn_loss_torch
-    from sorrel_amd.models.iqn_learner import _network_torch
 
     cpu = LC.make_model((model.qnetwork_local.head1.in_features // model.n_frames, model.n_frames, model.layer_size, model.n_quantiles,
                          model.action_space, model.batch_size), "cpu")
@@ -26,9 +25,9 @@ def eval_loss(model, args):
     taus = [t.cpu() for t in args["taus"]]
     with torch.no_grad():
         n = cpu.n_quantiles
-        a, _ = _network_torch(cpu.qnetwork_local, next_states, n, taus[0], mean=True)
-        b, _ = _network_torch(cpu.qnetwork_target, next_states, n, taus[1], mean=True)
-        c, t = _network_torch(cpu.qnetwork_local, states, n, taus[2], mean=True)
+        a, _ = cpu.qnetwork_local.forward_flat(next_states, n, taus[0], noise=False)
+        b, _ = cpu.qnetwork_target.forward_flat(next_states, n, taus[1], noise=False)
+        c, t = cpu.qnetwork_local.forward_flat(states, n, taus[2], noise=False)
         return float(_iqn_loss_torch(c, t, a, b, actions, rewards, dones, valid, cpu.GAMMA ** cpu.n_step)[0])
 
 
@@ -193,6 +192,69 @@ def test_take_action_uses_the_mean_weights_and_leaves_training_alone():
     want = net.get_qvalues(x).detach()
     net.train()
     assert torch.equal(q, want)
+
+
+@pytest.mark.parametrize("training", (False, True), ids=("eval", "training"))
+def test_the_torch_entry_points_agree_bit_for_bit(training, monkeypatch):
+    """``forward``, ``forward_fused`` and ``quantiles`` on the CPU and the learner's network call (acting's in eval mode, the step's in
+    training mode), with given taus and given noise."""
+    case = LC.load_fixture()[LC.tag_of(LC.SHAPES[0])]
+    args = LC.step_args(case["steps"][0], "cpu")
+    x, taus, eps = args["batch"][0], args["taus"][2], args["noise"][12:18]
+    B, N = taus.shape
+    net = LC.put_state(LC.make_model(case["shape"], "cpu"), case["snaps"][0]).qnetwork_local.train(training)
+    layers = (net.ff_1, net.advantage, net.value)
+
+    def held():
+        return [e for layer in layers for e in (layer.epsilon_weight, layer.epsilon_bias)]
+
+    got = {}
+    got["learner"] = net.forward_flat(x.view(B, -1), N, taus, noise=training, eps=eps if training else None)   # (copies eps into the layers)
+    if training:
+        assert all(torch.equal(a, b) for a, b in zip(held(), eps))
+    monkeypatch.setattr(torch.Tensor, "normal_", lambda t, *a, **k: t)             # the other calls apply the noise the layers hold
+    got["forward_fused"] = net.forward_fused(x, taus=taus)
+    res = net.quantiles(x, taus=taus)
+    got["quantiles"] = (res.quantiles, res.taus)
+    monkeypatch.setattr(torch, "rand", lambda *shape, **kw: taus.reshape(shape))
+    got["forward"] = net(x, N)
+    monkeypatch.undo()
+    for name, (q, t) in got.items():
+        assert tuple(q.shape) == (B, N, net.action_space) and tuple(t.shape) == (B, N, 1), name
+        LK.same_bits(q.detach().numpy(), got["forward"][0].detach().numpy(), "quantiles", (name, training))
+        LK.same_bits(t.numpy(), taus.numpy().reshape(B, N, 1), "taus", (name, training))
+    with torch.no_grad():
+        mean, _ = net.forward_flat(x.view(B, -1), N, taus, noise=False)
+    assert torch.equal(mean, got["forward"][0]) != training                       # the noise shows where it is applied, and only there
+
+
+def test_actor_and_learner_act_alike_on_the_cpu():
+    from sorrel_amd.models import IQNActor
+
+    obs, n_frames, L, N, A, B = LC.SHAPES[0]
+    learner = LC.make_model(LC.SHAPES[0], "cpu")
+    local = learner.qnetwork_local
+    with torch.no_grad():
+        for name in ("ff_1", "advantage", "value"):
+            getattr(local, name).sigma_weight.fill_(0.5)   # noise would show
+            getattr(local, name).epsilon_weight.normal_()
+    actor = IQNActor((obs,), A, layer_size=L, n_quantiles=N, n_frames=n_frames, seed=1)
+    actor.net.load_state_dict(local.state_dict())
+    nets = (actor.net, local)
+    flags = [[m.training for m in net.modules()] for net in nets]
+    assert flags[0] == [False] * len(flags[0]) and flags[1] == [True] * len(flags[1])
+    buffers = [{k: v.clone() for k, v in net.state_dict().items()} for net in nets]
+    x = torch.randn(B, obs * n_frames)
+    got = []
+    for model in (actor, learner):
+        torch.manual_seed(7)                               # the same taus
+        got.append(model.take_action(x))
+    for q in got:
+        assert q.shape == (B, A) and q.dtype == torch.float32 and not q.requires_grad
+    LK.same_bits(got[0].numpy(), got[1].numpy(), "action values")
+    assert [[m.training for m in net.modules()] for net in nets] == flags
+    for net, before in zip(nets, buffers):
+        assert all(torch.equal(v, before[k]) for k, v in net.state_dict().items())
 
 
 def test_hooks_are_checked():
