@@ -403,6 +403,7 @@ EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 _torch = None        # torch, kept by load() (imported there, not here: importing this module stays free of it)
+raw_stream = None    # load(): raw_stream(index) = the caller's current stream on device `index`, as the integer the library takes
 
 
 class SgwError(RuntimeError):
@@ -441,6 +442,9 @@ def load():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib, _torch = lib, torch
+    global raw_stream
+    # the private accessor PyTorch's own compilers use where it exists: the public one costs ~5 us per call, a third of a small-batch step
+    raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda index: torch.cuda.current_stream(index).cuda_stream)
     # tools pass dispatcher options to child processes as SGW_OPTIONS="key=value,key=value": read HERE, by the Python
     # tooling -- the library itself reads no environment variable except SGW_DEBUG
     for item in filter(None, os.environ.get("SGW_OPTIONS", "").replace(";", ",").split(",")):
@@ -535,25 +539,47 @@ def jit_stats() -> dict:
 _functions = {}     # launch(): the library's functions by name, looked up once (the small shapes are bound by the host)
 
 
+class _NoSwitch:
+    """Context manager that does nothing: the device is already the current one."""
+
+    def __enter__(self):
+        return None
+
+    def __exit__(self, *exc):
+        return False
+
+
+_NO_SWITCH = _NoSwitch()
+
+
+def on_device(index: int):
+    """Context that makes device ``index`` current; a no-op object when it already is (the usual case -- entering
+    ``torch.cuda.device`` costs several microseconds)."""
+    return _NO_SWITCH if _torch.cuda.current_device() == index else _torch.cuda.device(index)
+
+
+def call(index: int, fn, *args) -> None:
+    """THE library call: ``fn(*args)`` with device ``index`` current for it (the library launches on the current device; the pointers
+    and the stream among ``args`` belong to that device), a non-zero return code raised as ``check`` raises it.  No context manager
+    where the device is current already, nothing allocated, no synchronisation: legal inside a stream capture."""
+    if _torch.cuda.current_device() == index:
+        code = fn(*args)
+    else:
+        with _torch.cuda.device(index):
+            code = fn(*args)
+    if code:
+        check(code)
+
+
 def launch(name: str, desc, device, *leading) -> None:
-    """One descriptor call ``name(*leading, &desc, stream)`` on ``device``'s current stream, with ``device`` current for it (the library
-    launches on the current device; the descriptor's pointers and the stream belong to ``device``).  As ``GridEngine`` does it: the raw
-    stream handle, and no device switch where ``device`` is current already."""
+    """One descriptor call ``name(*leading, &desc, stream)`` on ``device``'s current stream, through ``call``."""
     fn = _functions.get(name)
     if fn is None:
         fn = _functions[name] = getattr(load(), name)
-    cuda = _torch.cuda
-    current = cuda.current_device()
-    index = current if device.index is None else device.index
-    raw = getattr(_torch._C, "_cuda_getCurrentRawStream", None)
-    stream = C.c_void_p(raw(index) if raw is not None else cuda.current_stream(index).cuda_stream)
-    if index == current:
-        code = fn(*leading, C.byref(desc), stream)
-    else:
-        with cuda.device(index):
-            code = fn(*leading, C.byref(desc), stream)
-    if code:
-        check(code)
+    index = device.index
+    if index is None:
+        index = _torch.cuda.current_device()
+    call(index, fn, *leading, C.byref(desc), raw_stream(index))
 
 
 def workspace(nbytes: int, device):

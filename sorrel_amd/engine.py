@@ -8,26 +8,23 @@ device raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import itertools
+import math
 from typing import Optional
 
 import torch
 
 from . import _native as N
+from ._check import check_tensor, refuse, tensor_ok
 from .spec import WorldSpec, alloc_grid, resolve_device
 
 
-class _NoSwitch:
-    """Context manager that does nothing: the engine's device is already the current one."""
-
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_SWITCH = _NoSwitch()
+def _index_vector(name, t, n: int, device) -> int:
+    """The pointer of an int64 vector of which a kernel reads the first ``n`` entries."""
+    if check_tensor(name, t, torch.int64, (...,), device).numel() < n:
+        refuse(name, t, torch.int64, f"at least {n} elements", device)
+    return t.data_ptr()
 
 
 class GridEngine:
@@ -52,6 +49,10 @@ class GridEngine:
             raise N.SgwError("no HIP device visible to PyTorch; the step/observe path has no CPU fallback")
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self._lib = N.load()
+        # every library call with a return code goes through N.call on the engine's device: self._call(self._lib.sgw_x, *args).  Bound
+        # here (no Python frame of the engine's own per call); the caller's current stream on that device is self._stream(), an integer
+        self._call = functools.partial(N.call, self._dev_index)
+        self._stream = functools.partial(N.raw_stream, self._dev_index)
         self.uid = next(GridEngine._uids)        # names this engine in caches (id() values are reused once an object is gone)
         if GridEngine._pending_closes and not torch.cuda.is_current_stream_capturing():
             GridEngine.drain_pending_closes()    # (engines dropped inside an earlier capture: their handles are destroyed no later than here)
@@ -76,16 +77,11 @@ class GridEngine:
             avail = g.untyped_storage().nbytes() - g.storage_offset()
             self.config.grid_env_stride = pad if avail >= pad else 0
         self._h = C.c_void_p()
-        with self._on_device():
-            N.check(self._lib.sgw_create(C.byref(self.config), C.byref(self._h)))
+        self._call(self._lib.sgw_create, C.byref(self.config), C.byref(self._h))
 
         def adopt(name, shape, dtype):
             t = tensors.get(name)
-            if t is None:
-                return torch.zeros(shape, dtype=dtype, device=dev)
-            if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
-                raise ValueError(f"tensor {name!r} must be contiguous {dtype} {tuple(shape)} on {dev}")
-            return t
+            return torch.zeros(shape, dtype=dtype, device=dev) if t is None else check_tensor(name, t, dtype, shape, dev)
 
         # state tensors may be adopted from the caller (the batched Gridworld owns them)
         self.agent_pos = adopt("agent_pos", (E, A, 2), torch.uint8)
@@ -99,7 +95,7 @@ class GridEngine:
             raise ValueError("obs_dtype must be torch.float32 or torch.uint8")
         self.obs_dtype = obs_dtype
         if obs_dtype == torch.uint8:
-            N.check(self._lib.sgw_set_obs_format(self._h, N.OBS_U8))
+            self._call(self._lib.sgw_set_obs_format, self._h, N.OBS_U8)
         self.obs = (torch.zeros((E,) + spec.obs_shape, dtype=obs_dtype, device=dev) if allocate_obs else None)
         self.epoch = 0
         self.turn = 0
@@ -113,20 +109,17 @@ class GridEngine:
         if spec.agent_rule == N.AGENT_RULE_TAG:
             self.agent_state = adopt("agent_state", (E, A), torch.uint8)
             self.state_at_pov = torch.zeros((E, A), dtype=torch.uint8, device=dev)
-            with self._on_device():
-                N.check(self._lib.sgw_bind_agent_state(self._h, self._ptr(self.agent_state), self._ptr(self.state_at_pov)))
-                if "agent_state" not in tensors:
-                    N.check(self._lib.sgw_init_agent_state(self._h, self._ptr(self.agent_state), self._stream()))
+            self._call(self._lib.sgw_bind_agent_state, self._h, self.agent_state.data_ptr(), self.state_at_pov.data_ptr())
+            if "agent_state" not in tensors:
+                self._call(self._lib.sgw_init_agent_state, self._h, self.agent_state.data_ptr(), self._stream())
         # per-env facing of each agent, 0 up / 1 right / 2 down / 3 left (Cleanup's beams)
         self.agent_dir = None
         if spec.agent_rule == N.AGENT_RULE_CLEANUP:
             self.agent_dir = tensors.get("agent_dir")
             if self.agent_dir is None:
                 self.agent_dir = torch.full((E, A), 2, dtype=torch.uint8, device=dev)   # CleanupAgent.__init__: facing down (agents.py:74); like Tag's flag it survives resets
-            elif tuple(self.agent_dir.shape) != (E, A) or self.agent_dir.dtype != torch.uint8 or self.agent_dir.device != dev \
-                    or not self.agent_dir.is_contiguous():
-                raise ValueError("agent_dir must be contiguous uint8 [E, A] on the engine's device")
-            N.check(self._lib.sgw_bind_agent_dir(self._h, self._ptr(self.agent_dir)))
+            check_tensor("agent_dir", self.agent_dir, torch.uint8, (E, A), dev)
+            self._call(self._lib.sgw_bind_agent_dir, self._h, self.agent_dir.data_ptr())
 
         # what every agent stepped on this turn (uint8 [E, A]; N.NO_TARGET: invalid action / outside the grid): on request only
         self.target_types = None
@@ -143,14 +136,13 @@ class GridEngine:
         ``GamblingAgent.act`` counts as an encounter.  ``t``: True allocates the tensor, a tensor adopts it, None / False unbinds."""
         E, A = self.num_envs, self.spec.num_agents
         if t is None or t is False:
-            N.check(self._lib.sgw_bind_target_types(self._h, None))
+            self._call(self._lib.sgw_bind_target_types, self._h, None)
             self.target_types = None
             return None
         if t is True:
             t = self.target_types if self.target_types is not None else torch.full((E, A), N.NO_TARGET, dtype=torch.uint8, device=self.device)
-        if tuple(t.shape) != (E, A) or t.dtype != torch.uint8 or t.device != self.device or not t.is_contiguous():
-            raise ValueError("target_types must be contiguous uint8 [E, A] on the engine's device")
-        N.check(self._lib.sgw_bind_target_types(self._h, self._ptr(t)))
+        check_tensor("target_types", t, torch.uint8, (E, A), self.device)
+        self._call(self._lib.sgw_bind_target_types, self._h, t.data_ptr())
         self.target_types = t
         return t
 
@@ -161,7 +153,7 @@ class GridEngine:
         adopts a tensor (it is not zeroed: the library never clears the counts, the caller decides when), default a zeroed one.
         ``ValueError`` for what the library refuses: Tag agents, a slot outside ``[0, num_slots)``, ``num_slots`` outside 1..32."""
         if slot_of_type is None:
-            N.check(self._lib.sgw_bind_encounters(self._h, None, None, 0))
+            self._call(self._lib.sgw_bind_encounters, self._h, None, None, 0)
             self.encounters = None
             return None
         E, A, T = self.num_envs, self.spec.num_agents, int(self.config.num_types)
@@ -177,64 +169,46 @@ class GridEngine:
             raise ValueError(f"num_slots must be in 1..32, not {K}")
         if counts is None:
             counts = torch.zeros((E, A, K), dtype=torch.int64, device=self.device)
-        if tuple(counts.shape) != (E, A, K) or counts.dtype != torch.int64 or counts.device != self.device or not counts.is_contiguous():
-            raise ValueError(f"counts must be contiguous int64 [{E}, {A}, {K}] on the engine's device")
+        check_tensor("counts", counts, torch.int64, (E, A, K), self.device)
         table = (C.c_uint8 * T)(*slots)
-        with self._on_device():
-            N.check(self._lib.sgw_bind_encounters(self._h, self._ptr(counts), C.cast(table, C.c_void_p), K))
+        self._call(self._lib.sgw_bind_encounters, self._h, counts.data_ptr(), C.cast(table, C.c_void_p), K)
         self.encounters = counts
         return counts
 
     # ------------------------------------------------------------------ util
-    def _stream(self):
-        """The caller's current stream on the engine's device (raw handle; the private fast accessor PyTorch's own
-        compilers use where it exists -- the public one costs ~5 us per call, a third of a small-batch step)."""
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        if raw is not None:
-            return C.c_void_p(raw(self._dev_index))
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _on_device(self):
-        """Context that makes the engine's device current for a library call; a no-op object when it already is (the
-        usual case -- entering ``torch.cuda.device`` costs several microseconds per call)."""
-        return _NO_SWITCH if torch.cuda.current_device() == self._dev_index else torch.cuda.device(self.device)
+        """Context that makes the engine's device current for as long as a caller wants to hold it (``_FastPolicyTurn``: across the
+        agents' forward passes); a single call needs none, ``self._call`` sees to the device itself."""
+        return N.on_device(self._dev_index)
 
-    @staticmethod
-    def _ptr(t: Optional[torch.Tensor]):
-        return C.c_void_p(0 if t is None else t.data_ptr())
+    @property
+    def window_shape(self) -> tuple:
+        """``(E, C, V, V)``: one agent's window in every env."""
+        return (self.num_envs,) + tuple(self.spec.obs_shape[1:])
+
+    @property
+    def window_elems(self) -> int:
+        """``C * V * V``: the elements of one window (a replay row holds that many, plus ``row_tail``)."""
+        return math.prod(self.window_shape[1:])
+
+    def is_window_rows(self, t, tail: int = 0) -> bool:
+        """Whether ``t`` is one window (+ ``tail`` elements) per env as the kernels write it (``SGW_STEP_OBS_NEXT_PACKED``, the row
+        kernels): ``E`` contiguous rows of exactly ``C*V*V + tail`` elements of the engine's observation dtype on its device, whatever
+        the trailing shape (``[E, C, V, V]`` or a replay row ``[E, C*V*V]``)."""
+        return tensor_ok(t, self.obs_dtype, (self.num_envs, None, ...), self.device) \
+            and t.numel() == self.num_envs * (self.window_elems + tail)
 
     def _check_obs(self, t: torch.Tensor, name: str) -> torch.Tensor:
-        """An observation destination handed to a kernel as a raw pointer must be exactly what the kernel writes:
-        ``E * A * C * V * V`` elements of the engine's observation dtype, contiguous, on the engine's device --
-        anything else would be an out-of-bounds device write."""
-        want = (self.num_envs,) + tuple(self.spec.obs_shape)
-        if not torch.is_tensor(t) or t.dtype != self.obs_dtype or tuple(t.shape) != want or t.device != self.device \
-                or not t.is_contiguous():
-            got = (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t)
-            raise ValueError(f"{name} must be a contiguous {self.obs_dtype} tensor of shape {want} on {self.device} "
-                             f"(got {got}); the step kernel writes exactly that many bytes")
-        return t
+        """An observation destination: exactly the ``E * A * C * V * V`` elements the step kernel writes."""
+        return check_tensor(name, t, self.obs_dtype, (self.num_envs,) + tuple(self.spec.obs_shape), self.device)
 
     def _check_window(self, t: torch.Tensor, name: str, tail: int = 0) -> torch.Tensor:
-        """One window per env (``SGW_STEP_OBS_NEXT_PACKED``): exactly ``E * C * V * V`` contiguous elements of the engine's
-        observation dtype on its device, whatever the trailing shape (``[E, C, V, V]`` or a replay row ``[E, C*V*V]``)."""
-        per_env = 1
-        for d in self.spec.obs_shape[1:]:
-            per_env *= int(d)
-        per_env += tail
-        if not torch.is_tensor(t) or t.dtype != self.obs_dtype or t.device != self.device or not t.is_contiguous() \
-                or t.dim() < 2 or t.shape[0] != self.num_envs or t.numel() != self.num_envs * per_env:
-            got = (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t)
-            raise ValueError(f"{name} must be a contiguous {self.obs_dtype} tensor with {self.num_envs} rows of {per_env} "
-                             f"elements on {self.device} (got {got}); the step kernel writes exactly that many bytes")
+        if not self.is_window_rows(t, tail):
+            refuse(name, t, self.obs_dtype, f"{self.num_envs} rows of {self.window_elems + tail} elements", self.device)
         return t
 
     def _check_pos(self, t: torch.Tensor) -> torch.Tensor:
-        want = (self.num_envs, self.spec.num_agents, 2)
-        if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != want or t.device != self.device \
-                or not t.is_contiguous():
-            raise ValueError(f"pos must be a contiguous uint8 tensor of shape {want} on {self.device}")
-        return t
+        return check_tensor("pos", t, torch.uint8, (self.num_envs, self.spec.num_agents, 2), self.device)
 
     _pending_closes: list = []        # (library, handle) of engines dropped while a stream was capturing: destroyed by drain_pending_closes()
     _uids = itertools.count(1)
@@ -251,7 +225,7 @@ class GridEngine:
             if capturing:
                 GridEngine._pending_closes.append((self._lib, h))
             else:
-                self._lib.sgw_destroy(h)
+                self._lib.sgw_destroy(h)             # (not through _call, here and below: it returns nothing, and may run at interpreter shutdown)
 
     @classmethod
     def drain_pending_closes(cls) -> int:
@@ -275,9 +249,8 @@ class GridEngine:
         if epoch is not None:
             self.epoch = int(epoch)
         self.turn = 0
-        with self._on_device():
-            N.check(self._lib.sgw_reset(self._h, self._ptr(self.grid), self._ptr(self.agent_pos),
-                                        self._ptr(self.total_reward), self.epoch, self._stream()))
+        self._call(self._lib.sgw_reset, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.total_reward.data_ptr(),
+                   self.epoch, self._stream())
 
     def observe(self, agent_begin: int = 0, agent_end: Optional[int] = None, out: Optional[torch.Tensor] = None,
                 pos: Optional[torch.Tensor] = None):
@@ -288,25 +261,20 @@ class GridEngine:
             raise ValueError("engine was built with allocate_obs=False; pass `out`")
         pos = self.agent_pos if pos is None else self._check_pos(pos)
         agent_end = self.spec.num_agents if agent_end is None else agent_end
-        with self._on_device():
-            N.check(self._lib.sgw_observe(self._h, self._ptr(self.grid), self._ptr(pos), self._ptr(out),
-                                          agent_begin, agent_end, self._stream()))
+        self._call(self._lib.sgw_observe, self._h, self.grid.data_ptr(), pos.data_ptr(), out.data_ptr(), agent_begin, agent_end, self._stream())
         return out
 
     # ------------------------------------------------------------------ policy-driven turns without re-rendering
     def capabilities(self) -> int:
         """``N.CAP_OBSERVE_ROWS`` | ``N.CAP_ACT`` (include/sgw.h)."""
-        return int(self._lib.sgw_capabilities(self._h))
+        return int(self._lib.sgw_capabilities(self._h))       # (not through _call: the return value is the capability mask)
 
     def window_rows(self, dests=None):
         """The per-agent window destinations ``sgw_observe_rows`` / ``sgw_act`` take: ``(ctypes pointer array, env stride in
         elements, the tensors)``.  ``dests`` = one tensor per agent, each ``num_envs`` contiguous rows of exactly one window
         (``C*V*V`` elements of the engine's observation dtype, e.g. a row of that agent's replay buffer); default = the
         slots of the observation tensor ``self.obs[:, a]``."""
-        A = self.spec.num_agents
-        per_env = 1
-        for d in self.spec.obs_shape[1:]:
-            per_env *= int(d)
+        A, per_env = self.spec.num_agents, self.window_elems
         arr = (C.c_void_p * A)()
         if dests is None:
             if self.obs is None:
@@ -326,38 +294,41 @@ class GridEngine:
         agent's window of the swept grid into its own destination (``rows`` from ``window_rows``, exactly one window per env and row)."""
         arr, stride, _ = rows
         turn = self.turn if turn is None else turn
-        with self._on_device():
-            N.check(self._lib.sgw_sweep_observe_rows(self._h, self._ptr(self.grid), self._ptr(self.agent_pos), arr, stride, self.epoch, turn,
-                                                     N.STEP_SWEEP if sweep else 0, self._stream()))
+        self._call(self._lib.sgw_sweep_observe_rows, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), arr, stride, self.epoch, turn,
+                   N.STEP_SWEEP if sweep else 0, self._stream())
 
     def observe_rows(self, rows, agent_begin: int = 0, agent_end: Optional[int] = None):
         """Every agent's window, once, into its own destination (``rows`` from ``window_rows``): step 2 of a policy-driven
         turn.  Needs ``CAP_OBSERVE_ROWS``; otherwise ``observe()`` into the observation tensor does the same job."""
         arr, stride, _ = rows
         agent_end = self.spec.num_agents if agent_end is None else agent_end
-        with self._on_device():
-            N.check(self._lib.sgw_observe_rows(self._h, self._ptr(self.grid), self._ptr(self.agent_pos), arr, stride,
-                                               agent_begin, agent_end, self._stream()))
+        self._call(self._lib.sgw_observe_rows, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), arr, stride,
+                   agent_begin, agent_end, self._stream())
 
     _ACTION_KINDS = {torch.uint8: N.ACT_U8, torch.int32: N.ACT_I32, torch.int64: N.ACT_I64}
 
     def is_action_values(self, action) -> bool:
         """A policy's VALUE output -- float32 ``[E, n_actions]`` -- which ``act`` / ``turn_act`` take as it is (``SGW_ACT_QF32``: the
         kernel picks the first index of each row's maximum, and explores by ``turn_epsilon`` under the turn protocol)."""
-        return torch.is_tensor(action) and action.dim() == 2 and action.dtype == torch.float32 and action.device == self.device \
-            and tuple(action.shape) == (self.num_envs, self.spec.num_actions) and action.is_contiguous()
+        return tensor_ok(action, torch.float32, (self.num_envs, self.spec.num_actions), self.device)
+
+    def is_direct_action(self, action) -> bool:
+        """Whether the act launches take ``action`` as it is: ``[E]`` uint8 / int32 / int64, contiguous, on the device (a policy's output
+        needs no narrowing copy), or action values (``is_action_values``).  Anything else is copied into ``self.actions`` first."""
+        if not torch.is_tensor(action):
+            return False
+        if action.dtype in self._ACTION_KINDS:
+            return tensor_ok(action, action.dtype, (self.num_envs,), self.device)
+        return self.is_action_values(action)
 
     def _action_arg(self, action):
-        """(pointer, SGW_ACT_* kind) of a caller's action tensor: ``[E]`` uint8 / int32 / int64, or float32 ``[E, n_actions]`` action values."""
+        """(pointer, SGW_ACT_* kind) of a caller's action tensor, which must be a direct one (``is_direct_action``); ``None``: ``(0, 0)``."""
         if action is None:
             return 0, 0
-        if self.is_action_values(action):
-            return action.data_ptr(), N.ACT_QF32
-        kind = self._ACTION_KINDS.get(action.dtype)
-        if kind is None or action.device != self.device or action.numel() != self.num_envs or not action.is_contiguous():
-            raise ValueError(f"action must be a contiguous uint8 / int32 / int64 tensor of {self.num_envs} elements -- or float32 action values "
-                             f"[{self.num_envs}, {self.spec.num_actions}] -- on {self.device}")
-        return action.data_ptr(), kind
+        if not self.is_direct_action(action):
+            refuse("action", action, "uint8 / int32 / int64", f"shape [{self.num_envs}] -- or float32 action values "
+                   f"[{self.num_envs}, {self.spec.num_actions}] --", self.device)
+        return action.data_ptr(), self._ACTION_KINDS.get(action.dtype, N.ACT_QF32)
 
     def act(self, agent: int, rows=None, action: Optional[torch.Tensor] = None, reward_row: Optional[torch.Tensor] = None,
             action_row: Optional[torch.Tensor] = None):
@@ -370,24 +341,11 @@ class GridEngine:
         time in those rows -- e.g. the rows of the agent's replay buffer."""
         arr, stride = (None, 0) if rows is None else (rows[0], rows[1])
         E, dev = self.num_envs, self.device
-        prr = par = 0
         pa, kind = self._action_arg(action)
-        if reward_row is not None:
-            if reward_row.dtype != torch.float32 or reward_row.device != dev or reward_row.numel() != E or not reward_row.is_contiguous():
-                raise ValueError(f"reward_row must be a contiguous float32 tensor of {E} elements on {dev}")
-            prr = reward_row.data_ptr()
-        if action_row is not None:
-            if action_row.dtype != torch.int64 or action_row.device != dev or action_row.numel() != E or not action_row.is_contiguous():
-                raise ValueError(f"action_row must be a contiguous int64 tensor of {E} elements on {dev}")
-            par = action_row.data_ptr()
-        # (plain integers for the pointers: this call sits in the per-agent loop of a policy turn, where the host is the
-        # bottleneck below ~16 k envs)
-        with self._on_device():
-            rc = self._lib.sgw_act(self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), arr, stride,
-                                   self.rewards.data_ptr(), self.total_reward.data_ptr(), int(agent), pa or None, kind,
-                                   prr or None, par or None, self._stream())
-        if rc:
-            N.check(rc)
+        prr = None if reward_row is None else check_tensor("reward_row", reward_row, torch.float32, E, dev).data_ptr()
+        par = None if action_row is None else check_tensor("action_row", action_row, torch.int64, E, dev).data_ptr()
+        self._call(self._lib.sgw_act, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), arr, stride,
+                   self.rewards.data_ptr(), self.total_reward.data_ptr(), int(agent), pa or None, kind, prr, par, self._stream())
         return self.rewards[:, agent] if reward_row is None else reward_row
 
     def bind_row_tail(self, kind: int, table: Optional[torch.Tensor] = None):
@@ -397,16 +355,12 @@ class GridEngine:
         to ``window_rows`` then hold ``C*V*V + tail`` elements per env."""
         n = 0
         if kind == N.TAIL_POSITION_TABLE:
-            if not torch.is_tensor(table) or table.dtype != torch.float32 or table.device != self.device or not table.is_contiguous() \
-                    or table.dim() != 3 or tuple(table.shape[:2]) != (self.spec.height, self.spec.width):
-                raise ValueError(f"table must be a contiguous float32 [H, W, tail_len] tensor on {self.device}")
-            n = int(table.shape[2])
+            n = int(check_tensor("table", table, torch.float32, (self.spec.height, self.spec.width, None), self.device).shape[2])
         elif kind == N.TAIL_AGENT_IS_IT:
             n = 1
         if self.obs_dtype != torch.float32 and kind != N.TAIL_NONE:
             raise ValueError("row tails are float32 (the observation format must be float32)")
-        with self._on_device():
-            N.check(self._lib.sgw_bind_row_tail(self._h, int(kind), n, self._ptr(table) if kind == N.TAIL_POSITION_TABLE else None))
+        self._call(self._lib.sgw_bind_row_tail, self._h, int(kind), n, table.data_ptr() if kind == N.TAIL_POSITION_TABLE else None)
         self.row_tail, self._tail_table = n, table
 
     # ------------------------------------------------------------------ a whole policy turn as one capturable submission
@@ -417,10 +371,9 @@ class GridEngine:
         row), ``row`` = the ring row the NEXT turn fills, ``step`` = rows the ring advances per turn.  ``rings=None`` unbinds.
         Blocking; not for the inside of a capture."""
         A, E = self.spec.num_agents, self.num_envs
-        self._turn_rings = None
+        self._turn_rings, self._turn_row_elems = None, [0] * A
         if rings is None:
-            with self._on_device():
-                N.check(self._lib.sgw_turn_bind(self._h, None))
+            self._call(self._lib.sgw_turn_bind, self._h, None)
             return
         if len(rings) != A:
             raise ValueError(f"need one ring (or None) per agent ({A}), got {len(rings)}")
@@ -431,12 +384,11 @@ class GridEngine:
                 continue
             states, rewards, actions, dones, row, step = ring
             cap = None
-            for name, t, dt in (("states", states, self.obs_dtype), ("rewards", rewards, torch.float32), ("actions", actions, torch.int64),
-                                ("dones", dones, torch.float32)):
+            for name, t, dt, size in (("states", states, self.obs_dtype, (None, E, ...)), ("rewards", rewards, torch.float32, (None, E)),
+                                      ("actions", actions, torch.int64, (None, E)), ("dones", dones, torch.float32, (None, E))):
                 if t is None:
                     continue
-                if not torch.is_tensor(t) or t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() < 2 or t.shape[1] != E:
-                    raise ValueError(f"rings[{a}].{name} must be a contiguous {dt} tensor [capacity, {E}, ...] on {self.device}")
+                check_tensor(f"rings[{a}].{name}", t, dt, size, self.device)
                 if cap is not None and t.shape[0] != cap:
                     raise ValueError(f"rings[{a}]: states / rewards / actions disagree on the capacity")
                 cap = int(t.shape[0])
@@ -444,80 +396,57 @@ class GridEngine:
                 continue
             if states is not None:
                 rows.states[a] = states.data_ptr()
-                rows.row_elems[a] = states[0, 0].numel()
+                rows.row_elems[a] = self._turn_row_elems[a] = states[0, 0].numel()      # (turn_prev_rows writes rows of that length)
             if rewards is not None:
-                if rewards[0].numel() != E:
-                    raise ValueError(f"rings[{a}].rewards must be [capacity, {E}]")
                 rows.rewards[a] = rewards.data_ptr()
             if actions is not None:
-                if actions[0].numel() != E:
-                    raise ValueError(f"rings[{a}].actions must be [capacity, {E}]")
                 rows.actions[a] = actions.data_ptr()
             if dones is not None:
-                if dones[0].numel() != E:
-                    raise ValueError(f"rings[{a}].dones must be [capacity, {E}]")
                 rows.dones[a] = dones.data_ptr()
             rows.capacity[a], rows.row[a], rows.step[a] = cap, int(row), int(step)
             keep.append((states, rewards, actions, dones))
         self._turn_rings = keep            # (the device state holds raw pointers into these)
-        with self._on_device():
-            N.check(self._lib.sgw_turn_bind(self._h, C.byref(rows)))
+        self._call(self._lib.sgw_turn_bind, self._h, C.byref(rows))
 
     def turn_set(self, epoch: Optional[int] = None, turn: Optional[int] = None):
         """``sgw_turn_set``: the turn the device has counted up to (stream-ordered; ``Environment.reset`` -> ``(epoch, 0)``)."""
-        with self._on_device():
-            N.check(self._lib.sgw_turn_set(self._h, self.epoch if epoch is None else int(epoch), self.turn if turn is None else int(turn),
-                                           self._stream()))
+        self._call(self._lib.sgw_turn_set, self._h, self.epoch if epoch is None else int(epoch), self.turn if turn is None else int(turn),
+                   self._stream())
 
     def turn_begin(self, sweep: bool = True):
         """``sgw_turn_begin``: ``turn += 1`` on the device, then the sweep and EVERY agent's window into ``self.obs``."""
         if self.obs is None:
             raise ValueError("turn_begin needs the observation tensor (allocate_obs=True)")
-        with self._on_device():
-            rc = self._lib.sgw_turn_begin(self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), self.obs.data_ptr(),
-                                          self.rewards.data_ptr(), self.total_reward.data_ptr(), N.STEP_SWEEP if sweep else 0, self._stream())
-        if rc:
-            N.check(rc)
+        self._call(self._lib.sgw_turn_begin, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), self.obs.data_ptr(),
+                   self.rewards.data_ptr(), self.total_reward.data_ptr(), N.STEP_SWEEP if sweep else 0, self._stream())
         return self.obs
 
     def turn_act(self, agent: int, action: Optional[torch.Tensor] = None):
         """``sgw_turn_act``: ``act`` of one agent with the windows in ``self.obs``; reward and int64 action also go to the agent's ring
         row of the turn in flight (by the device's own row count)."""
         pa, kind = self._action_arg(action)
-        with self._on_device():
-            rc = self._lib.sgw_turn_act(self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), self.obs.data_ptr(),
-                                        self.rewards.data_ptr(), self.total_reward.data_ptr(), int(agent), pa or None, kind, self._stream())
-        if rc:
-            N.check(rc)
+        self._call(self._lib.sgw_turn_act, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), self.obs.data_ptr(),
+                   self.rewards.data_ptr(), self.total_reward.data_ptr(), int(agent), pa or None, kind, self._stream())
         return self.rewards[:, agent]
 
     def turn_begin_rows(self, rows, sweep: bool = True):
         """``sgw_turn_begin_rows``: the sweep alone, then every agent's window into its row of ``rows`` (``window_rows(dests)``) AND -- by
         the device's row count -- into its replay row of the turn in flight."""
         arr, stride, _ = rows
-        with self._on_device():
-            rc = self._lib.sgw_turn_begin_rows(self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), self.rewards.data_ptr(),
-                                               self.total_reward.data_ptr(), arr, stride, N.STEP_SWEEP if sweep else 0, self._stream())
-        if rc:
-            N.check(rc)
+        self._call(self._lib.sgw_turn_begin_rows, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(),
+                   self.rewards.data_ptr(), self.total_reward.data_ptr(), arr, stride, N.STEP_SWEEP if sweep else 0, self._stream())
 
     def turn_act_rows(self, agent: int, rows, action: Optional[torch.Tensor] = None):
         """``sgw_turn_act_rows``: ``act`` of one agent, the repairs written to the later agents' rows of ``rows`` and to their replay rows."""
         arr, stride, _ = rows
         pa, kind = self._action_arg(action)
-        with self._on_device():
-            rc = self._lib.sgw_turn_act_rows(self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), arr, stride,
-                                             self.rewards.data_ptr(), self.total_reward.data_ptr(), int(agent), pa or None, kind, self._stream())
-        if rc:
-            N.check(rc)
+        self._call(self._lib.sgw_turn_act_rows, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), arr, stride,
+                   self.rewards.data_ptr(), self.total_reward.data_ptr(), int(agent), pa or None, kind, self._stream())
         return self.rewards[:, agent]
 
     def turn_end(self, commit_windows: bool = True):
         """``sgw_turn_end``: the turn's windows -> the agents' ring rows, every ring advances."""
-        with self._on_device():
-            rc = self._lib.sgw_turn_end(self._h, self.obs.data_ptr() if (commit_windows and self.obs is not None) else None, self._stream())
-        if rc:
-            N.check(rc)
+        self._call(self._lib.sgw_turn_end, self._h, self.obs.data_ptr() if (commit_windows and self.obs is not None) else None, self._stream())
 
     # ------------------------------------------------------------------ stochastic policies
     def _policy_dist(self, dist):
@@ -532,11 +461,7 @@ class GridEngine:
         return t, (N.POLICY_F64 if t.dtype == torch.float64 else N.POLICY_F32), (N.POLICY_LOGITS if logits else N.POLICY_PROBS)
 
     def _policy_out(self, t, n, dtype, name):
-        if t is None:
-            return None
-        if not torch.is_tensor(t) or t.dtype != dtype or t.device != self.device or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements on {self.device}")
-        return t
+        return None if t is None else check_tensor(name, t, dtype, n, self.device)
 
     def policy_sample(self, dist, agent: int = 0, idx: Optional[torch.Tensor] = None, epoch: Optional[int] = None, turn: Optional[int] = None,
                       out_actions: Optional[torch.Tensor] = None, out_log_probs: Optional[torch.Tensor] = None,
@@ -550,8 +475,7 @@ class GridEngine:
         nothing and does not synchronise.  ``out_log_probs=False`` / ``out_entropy=False``: not wanted (not computed; None is returned)."""
         t, dtype, mode = self._policy_dist(dist)
         n = int(t.shape[0])
-        if idx is not None and (not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.device != self.device or idx.numel() != n or not idx.is_contiguous()):
-            raise ValueError(f"idx must be a contiguous int64 tensor of {n} elements on {self.device}")
+        self._policy_out(idx, n, torch.int64, "idx")
         acts = self._policy_out(out_actions, n, torch.int64, "out_actions")
         lps = None if out_log_probs is False else self._policy_out(out_log_probs, n, torch.float32, "out_log_probs")
         ents = None if out_entropy is False else self._policy_out(out_entropy, n, torch.float32, "out_entropy")
@@ -571,10 +495,7 @@ class GridEngine:
         d.seed, d.first_env = int(self.spec.seed) & 0xFFFFFFFFFFFFFFFF, self.first_env_id
         d.epoch, d.turn = int(self.epoch if epoch is None else epoch), int(self.turn if turn is None else turn)
         d.agent0, d.dist_type, d.mode = int(agent), dtype, mode
-        with self._on_device():
-            rc = self._lib.sgw_policy_sample(C.byref(d), self._stream())
-        if rc:
-            N.check(rc)
+        N.launch("sgw_policy_sample", d, self.device)
         return acts, lps, ents
 
     def turn_policy_sample(self, agent: int, dist, out_actions: torch.Tensor, log_prob_ring: Optional[torch.Tensor] = None,
@@ -591,16 +512,9 @@ class GridEngine:
         if acts is None:
             raise ValueError("turn_policy_sample writes its actions to out_actions (a fixed address a recorded turn can replay)")
         ents = self._policy_out(out_entropy, E, torch.float32, "out_entropy")
-        ring = log_prob_ring
-        if ring is not None and (not torch.is_tensor(ring) or ring.dtype != torch.float32 or ring.device != self.device or ring.dim() != 2
-                                 or ring.shape[1] != E or not ring.is_contiguous()):
-            raise ValueError(f"log_prob_ring must be a contiguous float32 [capacity, {E}] tensor on {self.device}")
-        with self._on_device():
-            rc = self._lib.sgw_turn_policy_sample(self._h, int(agent), t.data_ptr(), dtype, mode, acts.data_ptr(),
-                                                  ring.data_ptr() if ring is not None else None, ents.data_ptr() if ents is not None else None,
-                                                  self._stream())
-        if rc:
-            N.check(rc)
+        ring = None if log_prob_ring is None else check_tensor("log_prob_ring", log_prob_ring, torch.float32, (None, E), self.device)
+        self._call(self._lib.sgw_turn_policy_sample, self._h, int(agent), t.data_ptr(), dtype, mode, acts.data_ptr(),
+                   ring.data_ptr() if ring is not None else None, ents.data_ptr() if ents is not None else None, self._stream())
         return acts
 
     # ------------------------------------------------------------------ speculative policy turns
@@ -608,10 +522,7 @@ class GridEngine:
         """``[A, E, C*V*V]`` float32, agent-major: the windows the policies read in a speculative turn (``turn_resolve``).  Agents that
         share a model are one contiguous ``[A_g * E, C*V*V]`` batch of it.  ``rows``: the caller's own tensor of that shape -- e.g. the
         ``A`` rows of a shared replay ring this turn fills -- instead of the engine's scratch."""
-        A, E = self.spec.num_agents, self.num_envs
-        per_env = 1
-        for d in self.spec.obs_shape[1:]:
-            per_env *= int(d)
+        A, E, per_env = self.spec.num_agents, self.num_envs, self.window_elems
         if getattr(self, "_spec_state", None) is None:
             self._spec_state = torch.zeros((4, E, A), dtype=torch.uint8, device=self.device)      # env_done (the first E bytes of [0]), pristine, dirty, previous moves
             self._spec_list = torch.zeros((2, E * A), dtype=torch.int64, device=self.device)      # the dirty rows of the odd / even passes
@@ -621,22 +532,19 @@ class GridEngine:
         if rows is None:
             if self._spec_rows is None:
                 self._spec_rows = torch.zeros((A, E, per_env), dtype=torch.float32, device=self.device)
-            rows = self._spec_rows
-        elif tuple(rows.shape) != (A, E, per_env) or rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous():
-            raise ValueError(f"rows must be a contiguous float32 [{A}, {E}, {per_env}] tensor on {self.device}")
-        return rows
+            return self._spec_rows
+        return check_tensor("rows", rows, torch.float32, (A, E, per_env), self.device)
 
     def gather_rows(self, flat: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         """``flat[idx]`` for float32 rows (``sgw_gather_rows``: the dirty rows of a speculative pass as one contiguous batch) into a buffer
         the engine keeps; valid until the next call."""
+        check_tensor("flat", flat, torch.float32, (None, None), self.device)
+        check_tensor("idx", idx, torch.int64, (..., ), self.device)
         n, ne = int(idx.numel()), int(flat.shape[1])
         buf = getattr(self, "_gather_buf", None)
         if buf is None or buf.shape[1] != ne or buf.shape[0] < n:
             buf = self._gather_buf = torch.empty((max(n, 4096), ne), dtype=torch.float32, device=self.device)
-        if flat.dtype != torch.float32 or not flat.is_contiguous() or idx.dtype != torch.int64 or not idx.is_contiguous() or idx.device != self.device:
-            raise ValueError("gather_rows: float32 contiguous rows and a contiguous int64 index vector on the engine's device")
-        with self._on_device():
-            N.check(self._lib.sgw_gather_rows(flat.data_ptr(), ne, idx.data_ptr(), n, buf.data_ptr(), self._stream()))
+        self._call(self._lib.sgw_gather_rows, flat.data_ptr(), ne, idx.data_ptr(), n, buf.data_ptr(), self._stream())
         return buf[:n]
 
     def choose_actions(self, values: torch.Tensor, idx: Optional[torch.Tensor], epoch: int, turn: int) -> torch.Tensor:
@@ -647,12 +555,9 @@ class GridEngine:
         if values.dim() != 2 or values.shape[1] != self.spec.num_actions or not values.is_floating_point():
             raise ValueError(f"action values must be floating point [n, {self.spec.num_actions}]; got {values.dtype} {tuple(values.shape)}")
         values = values.to(device=self.device, dtype=torch.float32).contiguous()
-        if idx is not None and (idx.dtype != torch.int64 or idx.device != self.device or not idx.is_contiguous() or idx.numel() < n):
-            raise ValueError("choose_actions: idx must be a contiguous int64 vector of at least n entries on the engine's device")
         out = torch.empty((n,), dtype=torch.int64, device=self.device)
-        with self._on_device():
-            N.check(self._lib.sgw_choose_actions(self._h, values.data_ptr(), idx.data_ptr() if idx is not None else None, n, int(epoch), int(turn),
-                                                 out.data_ptr(), self._stream()))
+        self._call(self._lib.sgw_choose_actions, self._h, values.data_ptr(), None if idx is None else _index_vector("idx", idx, n, self.device),
+                   n, int(epoch), int(turn), out.data_ptr(), self._stream())
         return out
 
     def verify_rows(self, played: "GridEngine", rows: torch.Tensor) -> None:
@@ -660,14 +565,16 @@ class GridEngine:
         (``step(actions, sweep=False)``: its ``obs`` are the windows the agents really had, its ``state_at_pov`` Tag's flags); every row of
         ``rows`` ``[A, E, C*V*V + tail]`` that differs is rewritten and listed (``verify_count`` / ``verify_list``)."""
         A, E = self.spec.num_agents, self.num_envs
-        if rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous() or rows.dim() != 3 or tuple(rows.shape[:2]) != (A, E):
-            raise ValueError(f"rows must be a contiguous float32 [{A}, {E}, row] tensor on {self.device}")
+        check_tensor("rows", rows, torch.float32, (A, E, None), self.device)
+        self._check_obs(played.obs, "played.obs")            # (the kernel reads this engine's E * A windows there)
+        flags = None
+        if self.spec.agent_rule == N.AGENT_RULE_TAG:
+            flags = check_tensor("played.state_at_pov", played.state_at_pov, torch.uint8, (E, A), self.device).data_ptr()
         if getattr(self, "_verify_list", None) is None:
             self._verify_list = torch.zeros((E * A,), dtype=torch.int64, device=self.device)
             self._verify_ctr = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        with self._on_device():
-            N.check(self._lib.sgw_verify_rows(self._h, played.obs.data_ptr(), self._ptr(played.state_at_pov), rows.data_ptr(), int(rows.shape[2]),
-                                              self._verify_list.data_ptr(), self._verify_ctr.data_ptr(), self._stream()))
+        self._call(self._lib.sgw_verify_rows, self._h, played.obs.data_ptr(), flags, rows.data_ptr(), int(rows.shape[2]),
+                   self._verify_list.data_ptr(), self._verify_ctr.data_ptr(), self._stream())
 
     def verify_count(self) -> int:
         """How many rows the last ``verify_rows`` rewrote (synchronises: the one read-back per pass)."""
@@ -675,10 +582,9 @@ class GridEngine:
 
     def apply_actions(self, idx: Optional[torch.Tensor], fresh: torch.Tensor, n: int) -> None:
         """``sgw_apply_actions``: ``actions[e, a] = fresh[k]`` for the k-th row index ``a * E + e`` of ``idx`` (None: k itself), k < n."""
-        if fresh.dtype != torch.int64 or fresh.device != self.device or not fresh.is_contiguous() or fresh.numel() < n:
-            raise ValueError("apply_actions: fresh must be a contiguous int64 vector of at least n entries on the engine's device")
-        with self._on_device():
-            N.check(self._lib.sgw_apply_actions(self._h, self.actions.data_ptr(), None if idx is None else idx.data_ptr(), fresh.data_ptr(), int(n), self._stream()))
+        n = int(n)
+        self._call(self._lib.sgw_apply_actions, self._h, self.actions.data_ptr(), None if idx is None else _index_vector("idx", idx, n, self.device),
+                   _index_vector("fresh", fresh, n, self.device), n, self._stream())
 
     def speculation_windows(self, rows: Optional[torch.Tensor] = None, sweep_turn: Optional[int] = None) -> torch.Tensor:
         """Every agent's PRE-move window into ``speculation_rows(rows)``: ``sgw_observe_rows`` where the engine has a row kernel for the
@@ -717,21 +623,19 @@ class GridEngine:
         A, E = self.spec.num_agents, self.num_envs
         pn, n_new = 0, 0
         if new_actions is not None:
-            if new_actions.dtype != torch.int64 or new_actions.device != self.device or not new_actions.is_contiguous() or new_actions.dim() != 1 \
-                    or (pass_no == 1 and new_actions.numel() != A * E) or new_actions.numel() > A * E:
-                raise ValueError(f"new_actions must be a contiguous int64 vector on {self.device} ({A * E} elements in pass 1)")
+            check_tensor("new_actions", new_actions, torch.int64, (A * E,) if pass_no == 1 else (None,), self.device)
+            if new_actions.numel() > A * E:
+                refuse("new_actions", new_actions, torch.int64, f"at most {A * E} elements", self.device)
             pn, n_new = new_actions.data_ptr(), int(new_actions.numel())
-        for name, t, dt in (("reward_rows", reward_rows, torch.float32), ("action_rows", action_rows, torch.int64)):
-            if t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != A * E):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of [{A}, {E}] on {self.device}")
-        with self._on_device():
-            rc = self._lib.sgw_turn_resolve(self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), rows.data_ptr(),
-                                            int(rows.shape[2]), self.rewards.data_ptr(), self.total_reward.data_ptr(), st.data_ptr(),
-                                            self._spec_list.data_ptr(), self._spec_ctr.data_ptr(), pn or None, n_new,
-                                            None if reward_rows is None else reward_rows.data_ptr(),
-                                            None if action_rows is None else action_rows.data_ptr(), int(pass_no), self._stream())
-        if rc:
-            N.check(rc)
+        if reward_rows is not None:
+            check_tensor("reward_rows", reward_rows, torch.float32, A * E, self.device)
+        if action_rows is not None:
+            check_tensor("action_rows", action_rows, torch.int64, A * E, self.device)
+        self._call(self._lib.sgw_turn_resolve, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), self.actions.data_ptr(), rows.data_ptr(),
+                   int(rows.shape[2]), self.rewards.data_ptr(), self.total_reward.data_ptr(), st.data_ptr(),
+                   self._spec_list.data_ptr(), self._spec_ctr.data_ptr(), pn or None, n_new,
+                   None if reward_rows is None else reward_rows.data_ptr(),
+                   None if action_rows is None else action_rows.data_ptr(), int(pass_no), self._stream())
 
     def spec_count(self, pass_no: int) -> int:
         """How many rows pass ``pass_no`` rewrote (synchronises: the one read-back per pass)."""
@@ -747,38 +651,35 @@ class GridEngine:
         """``sgw_turn_prev_rows``: ``Buffer.current_state`` by the device's row count -- the ``count`` rows of the agent's bound replay
         states before the row the turn in flight fills, oldest first, into ``out`` ``[count, E, row_elems]`` (contiguous, the engine's
         observation dtype, on the device)."""
-        if not torch.is_tensor(out) or out.dtype != self.obs_dtype or out.device != self.device or not out.is_contiguous() \
-                or out.dim() < 2 or out.shape[0] != count or out.shape[1] != self.num_envs:
-            raise ValueError(f"out must be a contiguous {self.obs_dtype} tensor [{count}, {self.num_envs}, ...] on {self.device}")
-        with self._on_device():
-            N.check(self._lib.sgw_turn_prev_rows(self._h, int(agent), int(count), out.data_ptr(), self._stream()))
+        bound = getattr(self, "_turn_row_elems", None) or ()
+        row = bound[agent] if 0 <= agent < len(bound) else 0
+        if not row:
+            raise ValueError(f"agent {agent} has no replay states bound (turn_bind)")
+        count, E = int(count), self.num_envs
+        if check_tensor("out", out, self.obs_dtype, (count, E, ...), self.device).numel() != count * E * row:
+            refuse("out", out, self.obs_dtype, f"[{count}, {E}] rows of {row} elements, the bound ring's row length,", self.device)
+        self._call(self._lib.sgw_turn_prev_rows, self._h, int(agent), int(count), out.data_ptr(), self._stream())
         return out
 
     def turn_epsilon(self, epsilon: float, agent: int = -1):
         """``sgw_turn_epsilon``: the exploration rate of action-value acts (``turn_act*`` with float32 ``[E, n_actions]``) of one agent, or of
         every agent (``-1``): with that probability the act takes the engine's own uniform draw for (env, turn, agent) instead of the
         row's argmax.  Stream-ordered, kept on the device: a recorded turn follows it."""
-        with self._on_device():
-            N.check(self._lib.sgw_turn_epsilon(self._h, int(agent), float(epsilon), self._stream()))
+        self._call(self._lib.sgw_turn_epsilon, self._h, int(agent), float(epsilon), self._stream())
 
     def turn_state(self):
         """(epoch, turn, [row per agent]) as the device has counted them (synchronising)."""
         et = (C.c_uint32 * 2)()
         rows = (C.c_int64 * N.MAX_AGENTS)()
-        with self._on_device():
-            N.check(self._lib.sgw_turn_state(self._h, et, rows, self._stream()))
+        self._call(self._lib.sgw_turn_state, self._h, et, rows, self._stream())
         return int(et[0]), int(et[1]), [int(rows[a]) for a in range(self.spec.num_agents)]
 
     def observe_full(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The whole map as an observation, ``[E, C, H, W]`` (``ObservationSpec(full_view=True).observe``): every cell's
         appearance summed over the layers."""
         want = (self.num_envs, self.spec.num_channels, self.spec.height, self.spec.width)
-        if out is None:
-            out = torch.empty(want, dtype=self.obs_dtype, device=self.device)
-        elif tuple(out.shape) != want or out.dtype != self.obs_dtype or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous {self.obs_dtype} tensor of shape {want} on {self.device}")
-        with self._on_device():
-            N.check(self._lib.sgw_observe_full(self._h, self._ptr(self.grid), self._ptr(out), self._stream()))
+        out = torch.empty(want, dtype=self.obs_dtype, device=self.device) if out is None else check_tensor("out", out, self.obs_dtype, want, self.device)
+        self._call(self._lib.sgw_observe_full, self._h, self.grid.data_ptr(), out.data_ptr(), self._stream())
         return out
 
     def pick_obs_placement(self, candidates: int = 4, launches: int = 30) -> dict:
@@ -864,10 +765,9 @@ class GridEngine:
             obs = None
         agent_end = self.spec.num_agents if agent_end is None else agent_end
         epoch = self.epoch
-        with self._on_device():
-            N.check(self._lib.sgw_step(self._h, self._ptr(self.grid), self._ptr(self.agent_pos), self._ptr(actions),
-                                       self._ptr(obs), self._ptr(self.rewards), self._ptr(self.total_reward),
-                                       epoch, t, agent_begin, agent_end, flags, self._stream()))
+        self._call(self._lib.sgw_step, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), actions.data_ptr(),
+                   None if obs is None else obs.data_ptr(), self.rewards.data_ptr(), self.total_reward.data_ptr(),
+                   epoch, t, agent_begin, agent_end, flags, self._stream())
         if self.max_turns and t == self.max_turns and agent_end == self.spec.num_agents and not no_move:
             self.epoch = epoch + 1        # the library has reset every env for the next epoch (sgw_set_auto_reset)
             if turn is None:
@@ -890,10 +790,7 @@ class GridEngine:
 
         def per_turn(t, name, dtype, tail):
             """A caller-owned ``[T, *tail]`` tensor the kernels fill turn by turn through a raw pointer."""
-            want = (T,) + tuple(tail)
-            if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {want} on {self.device}")
-            return t, t[0].numel()
+            return check_tensor(name, t, dtype, (T,) + tuple(tail), self.device), math.prod(tail)
 
         flags = N.STEP_SWEEP if sweep else 0
         if actions is not None:                                  # scripted
@@ -908,10 +805,9 @@ class GridEngine:
         if not write_obs or obs is None:
             flags |= N.STEP_NO_OBS
             obs = None
-        with self._on_device():
-            N.check(self._lib.sgw_rollout(self._h, self._ptr(self.grid), self._ptr(self.agent_pos), self._ptr(act), self._ptr(obs),
-                                          self._ptr(rew), self._ptr(self.total_reward), self.epoch, self.turn + 1, T,
-                                          ts_obs, ts_act, ts_rew, flags, self._stream()))
+        self._call(self._lib.sgw_rollout, self._h, self.grid.data_ptr(), self.agent_pos.data_ptr(), act.data_ptr(),
+                   None if obs is None else obs.data_ptr(), rew.data_ptr(), self.total_reward.data_ptr(), self.epoch, self.turn + 1, T,
+                   ts_obs, ts_act, ts_rew, flags, self._stream())
         # the engine's own per-turn tensors hold the LAST turn, as after T calls of step()
         if act is not self.actions:
             self.actions.copy_(act[-1])
@@ -928,28 +824,22 @@ class GridEngine:
         self.max_turns = int(max_turns)
         if self.max_turns and self.episode_return is None:
             self.episode_return = torch.zeros((self.num_envs,), dtype=torch.float64, device=self.device)
-        with self._on_device():
-            N.check(self._lib.sgw_set_auto_reset(self._h, self.max_turns,
-                                                 self._ptr(self.episode_return if self.max_turns else None)))
+        self._call(self._lib.sgw_set_auto_reset, self._h, self.max_turns, self.episode_return.data_ptr() if self.max_turns else None)
 
     def random_actions(self, turn: Optional[int] = None):
         t = self.turn + 1 if turn is None else int(turn)
-        with self._on_device():
-            N.check(self._lib.sgw_random_actions(self._h, self._ptr(self.actions), self.epoch, t, self._stream()))
+        self._call(self._lib.sgw_random_actions, self._h, self.actions.data_ptr(), self.epoch, t, self._stream())
         return self.actions
 
     def reduce_metrics(self) -> torch.Tensor:
         """Device tensor ``[sum(total_reward), sum(total_reward**2), E, 0]`` (K4)."""
-        with self._on_device():
-            N.check(self._lib.sgw_reduce_metrics(self._h, self._ptr(self.total_reward), self._ptr(self.metrics),
-                                                 self._stream()))
+        self._call(self._lib.sgw_reduce_metrics, self._h, self.total_reward.data_ptr(), self.metrics.data_ptr(), self._stream())
         return self.metrics
 
     def status(self) -> int:
         """Synchronising read-and-clear of the device status word."""
         v = C.c_int32(0)
-        with self._on_device():
-            N.check(self._lib.sgw_get_status(self._h, C.byref(v), self._stream()))
+        self._call(self._lib.sgw_get_status, self._h, C.byref(v), self._stream())
         return int(v.value)
 
     def raise_on_status(self):
@@ -966,18 +856,18 @@ class GridEngine:
 
     # ------------------------------------------------------------------ timing
     def set_timing(self, enable: bool):
-        N.check(self._lib.sgw_set_timing(self._h, 1 if enable else 0))
+        self._call(self._lib.sgw_set_timing, self._h, 1 if enable else 0)
 
     def step_time_ms(self):
         ms, n = C.c_double(0.0), C.c_int64(0)
-        N.check(self._lib.sgw_get_step_time_ms(self._h, C.byref(ms), C.byref(n)))
+        self._call(self._lib.sgw_get_step_time_ms, self._h, C.byref(ms), C.byref(n))
         return float(ms.value), int(n.value)
 
     def step_times_ms(self, capacity: int = 1 << 16):
         """Per-launch durations (ms, HIP events on the launch stream) since the last read, oldest first."""
         buf = (C.c_float * capacity)()
         n = C.c_int64(0)
-        rc = self._lib.sgw_get_step_times_ms(self._h, buf, capacity, C.byref(n))
+        rc = self._lib.sgw_get_step_times_ms(self._h, buf, capacity, C.byref(n))      # (not through _call: 1 means "truncated", not an error)
         if rc < 0:
             N.check(rc)
         self.series_truncated = rc == 1          # launches beyond `capacity` / the library's sample cap were left out
@@ -985,9 +875,9 @@ class GridEngine:
 
     def set_wg_per_cu(self, n: int):
         """Launch tuning of the wave-per-env kernel: 0 automatic, 1..8 forced, -1 never capped (include/sgw.h)."""
-        N.check(self._lib.sgw_set_wg_per_cu(self._h, int(n)))
+        self._call(self._lib.sgw_set_wg_per_cu, self._h, int(n))
 
     def launch_info(self) -> str:
         buf = C.create_string_buffer(1024)
-        N.check(self._lib.sgw_launch_info(self._h, buf, 1024))
+        self._call(self._lib.sgw_launch_info, self._h, buf, 1024)
         return buf.value.decode()

@@ -594,14 +594,13 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
             eng = self._ensure_engine()
             seen = getattr(self, "_spec_seen", None)
             if seen is not None and seen[:2] == (self.epoch, self.turn):      # the last turn was a speculative one
-                nw = int(np.prod(eng.spec.obs_shape[1:]))                      # (rows of the generic form carry the pov's tail behind the window)
-                return seen[2][a][:, :nw].reshape((eng.num_envs,) + tuple(eng.spec.obs_shape[1:]))
+                return seen[2][a][:, :eng.window_elems].reshape(eng.window_shape)    # (rows of the generic form carry the pov's tail behind the window)
             return eng.obs[:, a]
         t = self._mixed_obs[a]
         g = self._agent_engine[a]
         if t is None or self.agents[a].observation_spec.full_view:
             return t
-        return t.view((g.num_envs,) + tuple(g.spec.obs_shape[1:]))
+        return t.view(g.window_shape)
 
     def rollout(self, turns: int) -> None:
         """``turns`` fused ``take_turn``s with ONE engine call (``sgw_rollout``: one launch with every env's grid resident
@@ -741,12 +740,12 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
                 # this turn's window of an agent that has not acted yet: rendered after the sweep, kept current by the act
                 # launches of the agents before it
                 dests = tw[1][2]
-                return eng.obs[:, who] if dests is None else dests[who].view((eng.num_envs,) + tuple(eng.spec.obs_shape[1:]))
+                return eng.obs[:, who] if dests is None else dests[who].view(eng.window_shape)
             if own and self._fresh_obs is not None and self._fresh_obs[:2] == (who, self.world.mutations):
                 # rendered by the launch that moved the previous agent (SGW_STEP_OBS_NEXT) -- into the observation tensor,
                 # or straight into the row of this agent's replay buffer that add_memory is about to fill
                 slot = self._fresh_obs[2]
-                return eng.obs[:, who] if slot is None else slot.view((eng.num_envs,) + tuple(eng.spec.obs_shape[1:]))
+                return eng.obs[:, who] if slot is None else slot.view(eng.window_shape)
             out = eng.obs if (own and eng.obs is not None) else eng.scratch_obs()
             eng.observe(who, who + 1, out=out)
             return out[:, who]
@@ -788,13 +787,7 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
         if acting is not None and mem is getattr(self.agents[acting].model, "memory", None):
             return None
         row = mem.states[mem.idx]
-        per_env = 1
-        for d in eng.spec.obs_shape[1:]:
-            per_env *= int(d)
-        if row.dtype != eng.obs_dtype or row.device != eng.device or not row.is_contiguous() or row.dim() < 2 \
-                or row.shape[0] != eng.num_envs or row.numel() != eng.num_envs * per_env:
-            return None
-        return row
+        return row if eng.is_window_rows(row) else None
 
     def _push_epsilon(self, eng, slots=None) -> None:
         """The exploration rates of the agents that act through action values, to the device's turn state when they change."""
@@ -888,9 +881,9 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
                 self._push_epsilon(eng, (a,))                         # (a recorded turn gets its epsilons before each replay)
         if eng.spec.has_drawn_values:            # a drawn value is keyed by the turn in flight, like the exploration draws
             self._keep_turn_state(eng)
+        # the policy's output goes to the act launches as it is where it can (no narrowing copy), else through eng.actions
+        direct = eng.is_direct_action(action)
         if self._mixed:                          # windows are rendered per agent at its pov: nothing to keep current
-            direct = values or (action.device == eng.device and action.dtype in eng._ACTION_KINDS and action.dim() == 1
-                                and action.shape[0] == eng.num_envs and action.is_contiguous())
             if not direct:
                 eng.actions[:, a].copy_(action)
             return eng.act(a, None, action=action if direct else None)
@@ -899,8 +892,6 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
             if tw is None or tw[0] != self.world.mutations or a < tw[2]:
                 raise RuntimeError("a captured policy turn cannot be recorded while host code edits the world between pov and act")
             tw[2] = a + 1
-            direct = values or (action.device == eng.device and action.dtype in eng._ACTION_KINDS and action.dim() == 1
-                                and action.shape[0] == eng.num_envs and action.is_contiguous())
             if not direct:
                 eng.actions[:, a].copy_(action)
             if self._capture_rows is not None:
@@ -909,10 +900,7 @@ class Environment(SpeculativeTurns, MixedSpecTurns, PolicyTurns, RecordedTurns, 
         if tw is not None:
             if tw[0] == self.world.mutations and a >= tw[2]:
                 tw[2] = a + 1                    # the windows of the agents after a stay current: sgw_act repairs them
-                # the policy's output goes to the kernel as it is (no narrowing copy); rewards and actions are also written
-                # where the agent's add_memory would copy them to
-                direct = values or (action.device == eng.device and action.dtype in eng._ACTION_KINDS and action.dim() == 1
-                                    and action.shape[0] == eng.num_envs and action.is_contiguous())
+                # rewards and actions are also written where the agent's add_memory would copy them to
                 if not direct:
                     eng.actions[:, a].copy_(action)
                 rr = ar = None

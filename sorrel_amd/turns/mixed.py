@@ -48,7 +48,7 @@ class MixedSpecTurns:
                 out = None
             self._mixed_obs[a] = g.observe_full(out)
             return self._mixed_obs[a]
-        shape = (g.num_envs,) + tuple(g.spec.obs_shape[1:])
+        shape = g.window_shape
         dest = self._replay_slot(a, None, g)
         if dest is None:
             dest = self._mixed_obs[a]

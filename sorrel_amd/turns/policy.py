@@ -3,7 +3,6 @@ from __future__ import annotations
 
 from typing import Optional
 
-import numpy as np
 import torch
 
 from sorrel_amd.agents.agent import Agent
@@ -52,8 +51,8 @@ class PolicyTurns:
         slots = self._replay_slots if dests is not None else None      # (buffer, row) per agent
         if dests is None and eng.row_tail:      # tailed rows without replay buffers to put them in: the environment's own
             if self._tail_rows is None:
-                per_env = int(np.prod(eng.spec.obs_shape[1:])) + eng.row_tail
-                self._tail_rows = [torch.zeros((eng.num_envs, per_env), dtype=torch.float32, device=eng.device) for _ in self.agents]
+                self._tail_rows = [torch.zeros((eng.num_envs, eng.window_elems + eng.row_tail), dtype=torch.float32, device=eng.device)
+                                   for _ in self.agents]
             dests = self._tail_rows
         rows = eng.window_rows(dests)
         if dests is not None and self.fuse_sweep_and_rows and caps & N.CAP_SWEEP_ROWS:      # (round 6: row tails, Tag / Cleanup worlds and worlds above 4 KiB too)
@@ -82,9 +81,6 @@ class PolicyTurns:
         eng = self._engine
         if not self.write_obs_into_replay:
             return None
-        per_env = 1
-        for d in eng.spec.obs_shape[1:]:
-            per_env *= int(d)
         taken, rows, self._replay_slots = {}, [], []
         for agent in self.agents:
             mem = getattr(agent.model, "memory", None)
@@ -97,8 +93,7 @@ class PolicyTurns:
                 return None
             i = (mem.idx + k) % mem.capacity
             row = mem.states[i]
-            if row.dtype != eng.obs_dtype or row.device != eng.device or not row.is_contiguous() or row.dim() < 2 \
-                    or row.shape[0] != eng.num_envs or row.numel() != eng.num_envs * (per_env + eng.row_tail):
+            if not eng.is_window_rows(row, eng.row_tail):
                 return None
             rows.append(row)
             self._replay_slots.append((mem, i))
@@ -121,13 +116,14 @@ class _FastPolicyTurn:
         if env._mixed or not env.patch_windows or not env.write_obs_into_replay or eng.obs is None \
                 or eng.obs_dtype != torch.float32 or not (caps & N.CAP_ACT) or not (caps & N.CAP_OBSERVE_ROWS):
             return None
-        per_env = int(np.prod(eng.spec.obs_shape[1:])) + eng.row_tail       # (the engine writes what pov appends behind the window: Tag, Cleanup)
+        per_env = eng.window_elems + eng.row_tail       # (the engine writes what pov appends behind the window: Tag, Cleanup)
         taken, agents = {}, []
         for agent in env.agents:
             mem = getattr(agent.model, "memory", None)
+            # (every row of the ring, mem.states[i], is then one the engine can write: run_turn addresses them by i * row bytes)
             if not env._standard_hooks(agent) or type(agent).act is not MovingAgent.act or not isinstance(mem, Buffer) or mem.n_frames != 1 \
-                    or mem.extra_data or mem.num_envs != eng.num_envs or mem.device != eng.device or mem.states.dtype != torch.float32 \
-                    or not mem.states.is_contiguous() or mem.states[0, 0].numel() != per_env or getattr(agent.model, "device_random", False):
+                    or mem.extra_data or not mem.states.is_contiguous() or not eng.is_window_rows(mem.states[0], eng.row_tail) \
+                    or getattr(agent.model, "device_random", False):
                 return None
             k = taken.get(id(mem), 0)                 # agents that share a ring fill consecutive rows, in list order
             taken[id(mem)] = k + 1
@@ -212,6 +208,7 @@ class _FastPolicyTurn:
                     mem.add(state, eng.actions[:, a], reward, agent.is_done(world))
                     continue
                 else:
+                    # (eng.is_direct_action / is_action_values, written out here and above: two calls less per agent in the loop's common case)
                     kind = self.kinds.get(action.dtype)
                     if kind is None or action.device != dev or action.dim() != 1 or action.shape[0] != E or not action.is_contiguous():
                         eng.actions[:, a].copy_(action)

@@ -70,9 +70,7 @@ class RecordedTurns:
             return None
         if eng.obs is None or not self.patch_windows:
             return None
-        per_env = 1
-        for d in eng.spec.obs_shape[1:]:
-            per_env *= int(d)
+        per_env = eng.window_elems
         window_bytes = eng.num_envs * len(self.agents) * per_env * (4 if eng.obs_dtype == torch.float32 else 1)
         limit = self.capture_max_window_bytes
         if self.fast_policy_loop and self._fast_plan(eng) is not None:

@@ -3,7 +3,6 @@ from __future__ import annotations
 
 from typing import Optional
 
-import numpy as np
 import torch
 
 from sorrel_amd.agents.agent import Agent
@@ -79,8 +78,7 @@ class SpeculativeTurns:
         """``speculate_turns = True`` speculates where the model above says it is the faster turn (``"always"``: wherever it is possible)."""
         fixed, per_mb, per_agent, seq_fixed = self.speculation_cost_model_generic if getattr(self, "_spec_generic", False) else self.speculation_cost_model
         A = len(self.agents)
-        per_env = int(np.prod(eng.spec.obs_shape[1:]))
-        mb = eng.num_envs * A * per_env * 4 / 1e6
+        mb = eng.num_envs * A * eng.window_elems * 4 / 1e6
         return per_agent * A + seq_fixed > fixed + per_mb * mb
 
     def _speculation_groups_uncached(self, eng, N, Buffer):
@@ -92,7 +90,7 @@ class SpeculativeTurns:
         self._spec_generic = not (eng.capabilities() & N.CAP_RESOLVE) or bool(eng.row_tail)
         if self._spec_generic and not (eng.capabilities() & N.CAP_OBSERVE_ROWS):
             return None
-        per_env = int(np.prod(eng.spec.obs_shape[1:])) + (eng.row_tail if self._spec_generic else 0)
+        per_env = eng.window_elems + (eng.row_tail if self._spec_generic else 0)
         groups = []
         from sorrel_amd.buffers import RolloutBuffer
         for a, agent in enumerate(self.agents):
@@ -150,7 +148,7 @@ class SpeculativeTurns:
         E, A = eng.num_envs, len(self.agents)
         self._turn_windows = None
         played = self._spec_scratch_engine(eng)
-        per_env = int(np.prod(eng.spec.obs_shape[1:])) + eng.row_tail
+        per_env = eng.window_elems + eng.row_tail
         rows = self.__dict__.get("_spec_rows_generic")
         if rows is None or tuple(rows.shape) != (A, E, per_env) or rows.device != eng.device:
             rows = self.__dict__["_spec_rows_generic"] = torch.zeros((A, E, per_env), dtype=torch.float32, device=eng.device)

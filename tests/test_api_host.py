@@ -391,6 +391,85 @@ def test_engine_rejects_observation_destinations_the_kernel_would_overrun():
             eng._check_pos(bad)
 
 
+def test_check_tensor_passes_exactly_what_a_kernel_may_be_handed():
+    """``_check.check_tensor`` is the one test in front of every raw pointer the engine hands to the library: for each of its three size
+    forms the good tensor comes back as it is, and a non-tensor, another dtype, another shape, too few rows, a transposed view, another
+    element count and a tensor on another device (``meta``: no memory, no GPU) are each a ``ValueError`` -- for the dtype too."""
+    import torch
+
+    from sorrel_amd._check import check_tensor, tensor_ok
+
+    cpu, f32 = torch.device("cpu"), torch.float32
+    good = torch.zeros((6, 4, 5), dtype=f32)
+    everywhere = [("a non-tensor", "nope"), ("another dtype", good.double()), ("another dtype, narrower", good.to(torch.uint8)),
+                  ("too few rows", good[:5]), ("a transposed view", torch.zeros((4, 6, 5)).transpose(0, 1)),
+                  ("a strided view", torch.zeros((6, 4, 10))[:, :, ::2]), ("another device", torch.zeros((6, 4, 5), device="meta"))]
+    other_shape, other_count = ("another shape", torch.zeros((6, 5, 4))), ("another element count", torch.zeros((6, 4, 6)))
+    table = [
+        ("exact shape", (6, 4, 5), [other_shape, other_count, ("one dimension more", good[None])]),
+        ("exact shape, one extent free", (6, None, 5), [other_shape, other_count]),
+        ("leading shape + free tail", (6, 4, ...), [other_shape, ("fewer dimensions than the lead", torch.zeros((6,)))]),
+        ("element count", 120, [other_count, ("no elements", torch.zeros((0,)))]),
+    ]
+    for form, size, bad in table:
+        assert check_tensor("t", good, f32, size, cpu) is good, form
+        for what, t in everywhere + bad:
+            assert not tensor_ok(t, f32, size, cpu), (form, what)
+            with pytest.raises(ValueError, match="^t must be a contiguous torch.float32 tensor of .* on cpu; got "):
+                check_tensor("t", t, f32, size, cpu)
+    # what each form leaves free
+    assert tensor_ok(torch.zeros((6, 9, 5)), f32, (6, None, 5), cpu) and tensor_ok(torch.zeros((6, 4)), f32, (6, 4, ...), cpu)
+    assert tensor_ok(torch.zeros((6, 4, 2, 3)), f32, (6, 4, ...), cpu) and tensor_ok(torch.zeros((2, 60)), f32, 120, cpu)
+    assert tensor_ok(torch.zeros((0, 4)), f32, (...,), cpu) and tensor_ok(torch.zeros(()), f32, (), cpu)
+
+
+def test_engine_window_and_action_predicates():
+    """``GridEngine.window_elems`` / ``is_window_rows`` / ``is_direct_action``: what the environment and the turn loops ask before they
+    hand a replay row or a policy's output to the engine as it is.  Pure host logic on an engine without a device handle."""
+    import torch
+
+    from sorrel_amd.engine import GridEngine
+    from sorrel_amd.spec import treasurehunt_spec
+
+    eng = GridEngine.__new__(GridEngine)
+    eng.spec, eng.num_envs, eng.obs_dtype, eng.device, eng._h = treasurehunt_spec(16, 16, 4, 2), 6, torch.float32, torch.device("cpu"), None
+    eng.row_tail = 0
+    E, (_A, C, V, _V) = 6, eng.spec.obs_shape
+    assert (C, V) == (6, 5) and eng.window_elems == C * V * V == 150 and eng.window_shape == (E, C, V, V)
+    assert eng.is_window_rows(torch.zeros((E, C, V, V))) and eng.is_window_rows(torch.zeros((E, C * V * V)))
+    longer = torch.zeros((E, C * V * V + 1))
+    assert not eng.is_window_rows(longer) and not eng.is_window_rows(longer, tail=0) and eng.is_window_rows(longer, tail=1)
+    assert not eng.is_window_rows(torch.zeros((E, C * V * V)), tail=1)
+    for what, t in (("uint8", torch.zeros((E, C * V * V), dtype=torch.uint8)), ("E - 1 rows", torch.zeros((E - 1, C * V * V))),
+                    ("a non-contiguous view", torch.zeros((E, 2 * C * V * V))[:, ::2]), ("transposed", torch.zeros((C * V * V, E)).t()),
+                    ("one dimension", torch.zeros((E * C * V * V,))), ("another device", torch.zeros((E, C * V * V), device="meta")),
+                    ("a non-tensor", None)):
+        assert not eng.is_window_rows(t), what
+        with pytest.raises(ValueError):
+            eng._check_window(t, "row")
+    row = torch.zeros((E, C * V * V))
+    assert eng._check_window(row, "row") is row and eng._check_window(longer, "row", 1) is longer
+
+    nact = eng.spec.num_actions
+    for dtype in (torch.uint8, torch.int32, torch.int64):
+        assert eng.is_direct_action(torch.zeros((E,), dtype=dtype)), dtype
+    values = torch.zeros((E, nact), dtype=torch.float32)
+    assert eng.is_direct_action(values) and eng.is_action_values(values)
+    for what, t in (("int16", torch.zeros((E,), dtype=torch.int16)), ("[E, 1] int64", torch.zeros((E, 1), dtype=torch.int64)),
+                    ("float64 values", values.double()), ("[E + 1]", torch.zeros((E + 1,), dtype=torch.int64)),
+                    ("a strided view", torch.zeros((2 * E,), dtype=torch.int64)[::2]), ("strided values", torch.zeros((E, 2 * nact))[:, ::2]),
+                    ("values of another width", torch.zeros((E, nact + 1))), ("float32 [E]", torch.zeros((E,))),
+                    ("another device", torch.zeros((E,), dtype=torch.int64, device="meta")), ("a plain int", 3), ("None", None)):
+        assert not eng.is_direct_action(t), what
+        if t is not None:                        # (None is "no action tensor": the act reads self.actions)
+            with pytest.raises(ValueError):
+                eng._action_arg(t)
+    assert eng._action_arg(None) == (0, 0)
+    acts = torch.zeros((E,), dtype=torch.int32)
+    from sorrel_amd import _native as N
+    assert eng._action_arg(acts) == (acts.data_ptr(), N.ACT_I32) and eng._action_arg(values) == (values.data_ptr(), N.ACT_QF32)
+
+
 REFERENCE_STYLE_SCRIPT = '''
 # Written against the REFERENCE's import paths (the shape of sorrel/examples/treasurehunt/main.py + env.py), nothing from sorrel_amd:
 import numpy as np

@@ -412,3 +412,70 @@ def test_example_mains_run_with_default_device(torch_cuda):
     assert env.obs.device == world.device
     for mod in ("sorrel_amd.examples.treasurehunt.main", "sorrel_amd.examples.tag.main", "sorrel_amd.examples.cleanup.main"):
         runpy.run_module(mod, run_name="__main__")                             # 4096 envs, 2-3 short epochs each
+
+
+def test_engine_refuses_the_pointers_it_used_to_pass_unchecked(torch_cuda):
+    """``gather_rows``, ``apply_actions``, ``verify_rows`` and ``turn_prev_rows`` hand the library raw pointers: each refuses a bad
+    argument with ``ValueError`` before the library is reached, and a good call still does its work.  Every bad argument lives on the
+    engine's device and holds at least the bytes the kernel would touch, so a check that went missing fails this test and nothing else."""
+    torch = torch_cuda
+    from sorrel_amd.spec import treasurehunt_spec
+    from tests.gpu_common import make_engine
+
+    ws = treasurehunt_spec(9, 9, 2, 2, spawn_prob=0.05, seed=3)
+    E, A = 3, ws.num_agents
+    eng, played = make_engine(ws, E), make_engine(ws, E)
+    Nw = eng.window_elems
+    for e in (eng, played):
+        e.reset(0)
+
+    # gather_rows: flat[idx] of float32 rows
+    flat = torch.arange(A * E * Nw, dtype=torch.float32, device="cuda:0").view(A * E, Nw)
+    idx = torch.tensor([4, 0, 5], dtype=torch.int64, device="cuda:0")
+    assert torch.equal(eng.gather_rows(flat, idx), flat.index_select(0, idx))
+    for bad in (flat.view(A, E, Nw), flat.double()):                   # not [rows, row length]; a wider dtype
+        with pytest.raises(ValueError):
+            eng.gather_rows(bad, idx)
+    with pytest.raises(ValueError):
+        eng.gather_rows(flat, torch.zeros((6,), dtype=torch.int64, device="cuda:0")[::2])
+
+    # apply_actions: actions[e, a] = fresh[k] for the k-th row index a * E + e
+    every = torch.arange(A * E, dtype=torch.int64, device="cuda:0")
+    fresh = (every * 7 + 1) % ws.num_actions
+    eng.apply_actions(every, fresh, A * E)
+    assert torch.equal(eng.actions, fresh.view(A, E).t().to(torch.uint8))
+    before = eng.actions.clone()
+    zeros = torch.zeros((2 * A * E,), dtype=torch.int64, device="cuda:0")
+    for bad in (zeros.to(torch.int32), zeros[::2], zeros.double()):     # as many bytes in a narrower dtype; a strided view; not integers
+        with pytest.raises(ValueError):
+            eng.apply_actions(bad, fresh, A * E)
+    assert torch.equal(eng.actions, before)
+
+    # verify_rows: the rows against what a scratch engine's agents really saw
+    played.step(eng.actions, sweep=False, turn=1)
+    seen = played.obs.view(E, A, Nw).permute(1, 0, 2).contiguous()
+    rows = seen.clone()
+    eng.verify_rows(played, rows)
+    assert eng.verify_count() == 0 and torch.equal(rows, seen)
+    rows.zero_()
+    eng.verify_rows(played, rows)
+    assert eng.verify_count() == A * E and torch.equal(rows, seen)
+    for bad in (make_engine(ws, E, allocate_obs=False), make_engine(ws, E + 1)):      # no windows at all; another engine's size
+        with pytest.raises(ValueError):
+            eng.verify_rows(bad, rows)
+
+    # turn_prev_rows: the rows of the bound ring before the row the next turn fills, oldest first
+    CAP = 4
+    states = torch.arange(CAP * E * Nw, dtype=torch.float32, device="cuda:0").view(CAP, E, Nw)
+    eng.turn_bind([(states, None, None, None, 1, 1), None])
+    out = torch.empty((2, E, Nw), device="cuda:0")
+    assert eng.turn_prev_rows(0, 2, out) is out and torch.equal(out, states[[3, 0]])
+    for agent, bad in ((0, torch.empty((2, E, Nw + 1), device="cuda:0")),             # a row longer than the ring's
+                       (0, torch.empty((2, E, Nw), dtype=torch.float64, device="cuda:0")),
+                       (1, out)):                                                     # an agent without bound states
+        with pytest.raises(ValueError):
+            eng.turn_prev_rows(agent, 2, bad)
+    eng.turn_bind(None)
+    with pytest.raises(ValueError):
+        eng.turn_prev_rows(0, 2, out)
+    assert eng.status() == 0 and played.status() == 0
