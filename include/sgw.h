@@ -1150,6 +1150,33 @@ typedef struct sgw_noisy_weights_desc {
 } sgw_noisy_weights_desc;
 int sgw_noisy_weights(const sgw_noisy_weights_desc* desc, void* stream);
 
+/* ---- The learner clock: a learner's step recorded once and replayed (a graph's argument blocks are frozen, so what changes from one
+ * step to the next must be read from device memory) ----
+ * A learner's step takes three scalars that change with every step: `draw` of sgw_noisy_weights and `turn` of sgw_iqn_forward, which are
+ * both the count of steps done, and `num_starts` of sgw_sample, which grows while the replay ring fills.  The clock holds them in DEVICE
+ * memory, 8-byte aligned, filled by the caller; the *_clocked calls read them there, once, with a uniform load at the top of the kernel
+ * that needs them, and are otherwise the unclocked calls: every key formula, rule, limit and refusal above holds unchanged, and the
+ * results are bit for bit those of the unclocked call given the same scalar.
+ *   sgw_noisy_weights_clocked:  draw = clock->count (both words).  desc->draw must be 0.
+ *   sgw_iqn_forward_clocked:    the drawn taus' turn = (uint32_t)clock->count; epoch, seed, first_env, num_envs, agent0 and idx come from
+ *                               the descriptor.  desc->turn must be 0 and desc->taus NULL (given taus need no clock).
+ *   sgw_sample_clocked:         drawn indices only: desc->starts and desc->envs must be NULL; draw_count / draw as in sgw_sample.  The draws
+ *                               use num_starts = min(max(clock->num_starts, 1), desc->num_starts): desc->num_starts is the UPPER BOUND,
+ *                               checked against capacity and n_frames as sgw_sample checks it, and the clamp runs in the kernel, so no
+ *                               value in the clock makes a read leave the ring.
+ *   sgw_learn_clock_advance:    count += 1 (one thread), after the step's kernels on `stream`: a recorded chain's last node.
+ * All four refuse a NULL clock, a clock whose address is not a multiple of 8 and a non-zero scalar the clock replaces with SGW_EINVAL
+ * and the reason in sgw_last_error(), before anything is launched.  reserved is not read. */
+typedef struct sgw_learn_clock {
+    uint64_t count;              /* learner steps completed = the key of the step in flight */
+    int64_t num_starts;          /* ring rows a drawn sample may start from, now */
+    uint64_t reserved[2];        /* reserved: 0 */
+} sgw_learn_clock;
+int sgw_noisy_weights_clocked(const sgw_noisy_weights_desc* desc, const sgw_learn_clock* clock, void* stream);
+int sgw_iqn_forward_clocked(const sgw_iqn_forward_desc* desc, const sgw_learn_clock* clock, void* stream);
+int sgw_sample_clocked(const sgw_sample_desc* desc, const sgw_learn_clock* clock, void* stream);
+int sgw_learn_clock_advance(sgw_learn_clock* clock, void* stream);
+
 /* out6 = { instances compiled, loaded from the disk cache, reused in memory, refused, ms spent compiling, ms spent loading }
  * of this process so far. */
 int sgw_jit_stats(double* out6);

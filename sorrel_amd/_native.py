@@ -320,6 +320,12 @@ class SgwNoisyWeightsDesc(C.Structure):
     ]
 
 
+class SgwLearnClock(C.Structure):
+    """Mirror of ``struct sgw_learn_clock``: what the ``*_clocked`` calls read in DEVICE memory (the host builds its image and uploads it)."""
+
+    _fields_ = [("count", C.c_uint64), ("num_starts", C.c_int64), ("reserved", C.c_uint64 * 2)]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGW_LIB") or os.path.join(_HERE, "csrc", "libsgw.so")   # SGW_LIB: diagnostic builds (tools/)
 
@@ -393,6 +399,10 @@ PROTOTYPES = {
     "sgw_iqn_backward": (_rc, [C.POINTER(SgwIqnBackwardDesc), _vp]),
     "sgw_iqn_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
     "sgw_noisy_weights": (_rc, [C.POINTER(SgwNoisyWeightsDesc), _vp]),
+    "sgw_noisy_weights_clocked": (_rc, [C.POINTER(SgwNoisyWeightsDesc), _vp, _vp]),
+    "sgw_iqn_forward_clocked": (_rc, [C.POINTER(SgwIqnForwardDesc), _vp, _vp]),
+    "sgw_sample_clocked": (_rc, [C.POINTER(SgwSampleDesc), _vp, _vp]),
+    "sgw_learn_clock_advance": (_rc, [_vp, _vp]),
     "sgw_adam_plan_bytes": (_i64, [_i64, _i64]),
     "sgw_adam_plan": (_rc, [C.POINTER(SgwAdamTensor), _i64, _i32, _vp, _i64, C.POINTER(SgwAdamPlanInfo)]),
     "sgw_adam_step": (_rc, [C.POINTER(SgwAdamStepDesc), _vp]),
@@ -571,15 +581,21 @@ def call(index: int, fn, *args) -> None:
         check(code)
 
 
-def launch(name: str, desc, device, *leading) -> None:
-    """One descriptor call ``name(*leading, &desc, stream)`` on ``device``'s current stream, through ``call``."""
+def launch(name: str, desc, device, *leading, clock=None) -> None:
+    """One descriptor call ``name(*leading, &desc, stream)`` on ``device``'s current stream, through ``call``.  ``clock``: the device address
+    of an ``sgw_learn_clock``; the call is then the clocked twin ``name_clocked(*leading, &desc, clock, stream)``."""
+    if clock is not None:
+        name += "_clocked"
     fn = _functions.get(name)
     if fn is None:
         fn = _functions[name] = getattr(load(), name)
     index = device.index
     if index is None:
         index = _torch.cuda.current_device()
-    call(index, fn, *leading, C.byref(desc), raw_stream(index))
+    if clock is None:
+        call(index, fn, *leading, C.byref(desc), raw_stream(index))
+    else:
+        call(index, fn, *leading, C.byref(desc), clock, raw_stream(index))
 
 
 def workspace(nbytes: int, device):

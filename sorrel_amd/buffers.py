@@ -83,8 +83,9 @@ def _check_index_list(name, values, batch_size, bound, device):
     return host
 
 
-def _launch_sample(layout, n_frames, batch_size, outs, index, starts, envs, num_starts, count=None, seed=0):
-    """One ``sgw_sample`` call on the current stream.  ``outs`` = (states, next_states, actions, rewards, dones, valid) tensors."""
+def _launch_sample(layout, n_frames, batch_size, outs, index, starts, envs, num_starts, count=None, seed=0, clock=None):
+    """One ``sgw_sample`` call on the current stream.  ``outs`` = (states, next_states, actions, rewards, dones, valid) tensors.
+    ``clock`` (the device address of an ``sgw_learn_clock``): ``sgw_sample_clocked``, with ``num_starts`` the upper bound of the clock's."""
     from sorrel_amd import _native as N
 
     d = N.SgwSampleDesc()
@@ -101,7 +102,7 @@ def _launch_sample(layout, n_frames, batch_size, outs, index, starts, envs, num_
     d.scalar_turn_stride, d.scalar_env_stride = layout["cstr"]
     d.seed, d.draw = seed & 0xFFFFFFFFFFFFFFFF, 0
     d.n_frames, d.src_type, d.act_type = n_frames, layout["src"], layout["act"]
-    N.launch("sgw_sample", d, layout["device"])
+    N.launch("sgw_sample", d, layout["device"], clock=clock)
 
 
 def _sample_outputs(batch_size, n_frames, R, device):
@@ -640,16 +641,24 @@ class ReplaySampler:
     def num_starts(self) -> int:
         return max(1, self.ring.size - self.n_frames - 1)
 
+    def max_starts(self) -> int:
+        """``num_starts()`` of a full ring: the upper bound a clocked call hands to the kernel."""
+        return max(1, self.ring.capacity - self.n_frames - 1)
+
     def batch(self):
         """The storage ``sample`` fills, in the order it returns it."""
         s, ns, a, r, d, v = self._outs
         return s, a, r, ns, d, v
 
-    def sample(self, starts=None, envs=None):
+    def sample(self, starts=None, envs=None, clock=None):
+        """``clock``: the device address of an ``sgw_learn_clock`` whose ``num_starts`` the caller keeps at ``num_starts()``; the draws are then
+        bounded by what the clock holds when the kernel runs (``sgw_sample_clocked``), which is what a recorded call needs while the ring fills."""
         if (starts is None) != (envs is None):
             raise ValueError("starts and envs are both given or both None")
+        if clock is not None and (starts is not None or self.device.type != "cuda"):
+            raise ValueError("clock= bounds indices drawn on the device: starts and envs must be None")
         layout = _ring_layout(self.ring, self.agent)
-        hi, B = self.num_starts(), self.batch_size
+        hi, B = self.num_starts() if clock is None else self.max_starts(), self.batch_size
         if starts is not None:
             starts = _check_index_list("starts", starts, B, hi, self.device)
             envs = _check_index_list("envs", envs, B, layout["cols"], self.device)
@@ -670,5 +679,5 @@ class ReplaySampler:
                 starts = torch.from_numpy(starts).to(self.device) if isinstance(starts, np.ndarray) else starts
                 envs = torch.from_numpy(envs).to(self.device) if isinstance(envs, np.ndarray) else envs
             _launch_sample(layout, self.n_frames, B, self._outs, self.last_index, starts, envs, hi,
-                           count=self.draw_count if starts is None else None, seed=self.seed)
+                           count=self.draw_count if starts is None else None, seed=self.seed, clock=clock)
         return self.batch()

@@ -25,6 +25,7 @@
 // skip their stores.  A NaN or an infinity stays in its row: rows of A never mix.
 // No atomics, no cross-workgroup traffic: two runs give the same bits.  fp contract is off in every body; the chains are explicit fmaf.
 #pragma once
+#include "learn_clock.h"
 
 constexpr int kFwdM = 64;                     // rows of a tile (two 32-row MFMA tiles)
 constexpr int kFwdKT = 32;                    // k of a staged weight tile
@@ -170,8 +171,10 @@ __global__ __launch_bounds__(kFwdThreads) void iqn_head_kernel(const IqnFwdParam
     }
 }
 
-// second launch: everything behind the head for tiles of R whole states = R N quantile rows
-__global__ __launch_bounds__(kFwdThreads) void iqn_quantile_kernel(const IqnFwdParams p) {
+// second launch: everything behind the head for tiles of R whole states = R N quantile rows.  CLOCKED (iqn_quantile_clocked_kernel): the drawn
+// taus' turn is the low word of the learner clock's count, read once here; the epoch is the descriptor's
+template <bool CLOCKED>
+__device__ __forceinline__ void iqn_quantile_tiles(const IqnFwdParams& p, const sgw_learn_clock* clock) {
 #pragma clang fp contract(off)
     __shared__ float X[kFwdM * kFwdXS];       // z, then y: [quantile row][L padded to whole column tiles]
     __shared__ float Cb[kFwdM * kFwdCS];      // the cosines [quantile row][64]; then adv_0 .. adv_(A-1), val of every quantile row
@@ -181,7 +184,9 @@ __global__ __launch_bounds__(kFwdThreads) void iqn_quantile_kernel(const IqnFwdP
     const int tid = threadIdx.x;
     const int N = p.N, A = p.A, L = p.L, R = p.R, CT = (L + 31) >> 5;
     uint32_t epoch = p.epoch, turn = p.turn;
-    if (p.ts) {                               // (uniform: scalar loads)
+    if constexpr (CLOCKED) {
+        turn = (uint32_t)learn_clock_count(clock);
+    } else if (p.ts) {                        // (uniform: scalar loads)
         epoch = p.ts->epoch;
         turn = p.ts->turn + 1u;
     }
@@ -293,4 +298,11 @@ __global__ __launch_bounds__(kFwdThreads) void iqn_quantile_kernel(const IqnFwdP
         }
         __syncthreads();                      // the next tile rewrites tau_s and Cb
     }
+}
+
+__global__ __launch_bounds__(kFwdThreads) void iqn_quantile_kernel(const IqnFwdParams p) { iqn_quantile_tiles<false>(p, nullptr); }
+
+// sgw_iqn_forward_clocked's second launch (the head draws nothing: iqn_head_kernel serves both)
+__global__ __launch_bounds__(kFwdThreads) void iqn_quantile_clocked_kernel(const IqnFwdParams p, const sgw_learn_clock* clock) {
+    iqn_quantile_tiles<true>(p, clock);
 }

@@ -8,6 +8,7 @@
 // block, so a drawn block is computed once.  Tensors are aligned to their element only (value.bias has one element, a bias follows its
 // weight anywhere), so every load and store is one dword.  No atomics, no LDS, no scratch; the product is rounded before the sum.
 #pragma once
+#include "learn_clock.h"
 
 constexpr int kNoisyChunk = 4 * kBlock;
 
@@ -24,10 +25,11 @@ struct NoisyParams {
     uint32_t seed_lo, seed_hi, draw_lo, draw_hi;
 };
 
-// the four normals of Philox block `blk`: Box-Muller over the word pairs (x, y) and (z, w)
-__device__ __forceinline__ void noisy_normals(const NoisyParams& p, const uint32_t c3, const uint32_t blk, float (&n)[4]) {
+// the four normals of Philox block `blk` of draw (draw_lo, draw_hi): Box-Muller over the word pairs (x, y) and (z, w)
+__device__ __forceinline__ void noisy_normals(const NoisyParams& p, const uint32_t draw_lo, const uint32_t draw_hi, const uint32_t c3, const uint32_t blk,
+                                              float (&n)[4]) {
 #pragma clang fp contract(off)
-    const U4 w = philox4x32_10(blk, p.draw_lo, p.draw_hi, c3, p.seed_lo, p.seed_hi);
+    const U4 w = philox4x32_10(blk, draw_lo, draw_hi, c3, p.seed_lo, p.seed_hi);
     const uint32_t wa[2] = {w.x, w.z}, wb[2] = {w.y, w.w};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -40,8 +42,9 @@ __device__ __forceinline__ void noisy_normals(const NoisyParams& p, const uint32
     }
 }
 
+// one chunk of one job; the draw's two words come from the argument block (noisy_kernel) or from the learner clock (noisy_clocked_kernel)
 template <bool BACKWARD>
-__global__ __launch_bounds__(kBlock) void noisy_kernel(const NoisyParams p) {
+__device__ __forceinline__ void noisy_chunk(const NoisyParams& p, const uint32_t draw_lo, const uint32_t draw_hi) {
 #pragma clang fp contract(off)
     const int chunk = (int)blockIdx.x;
     int ji = 0;
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void noisy_kernel(const NoisyParams p) {
         float* __restrict__ out = jb.out;
         float* __restrict__ out_eps = jb.out_eps;
         float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (!eps_in) noisy_normals(p, jb.c3, (uint32_t)(i0 >> 2), n);
+        if (!eps_in) noisy_normals(p, draw_lo, draw_hi, jb.c3, (uint32_t)(i0 >> 2), n);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int64_t i = i0 + k;
@@ -79,4 +82,15 @@ __global__ __launch_bounds__(kBlock) void noisy_kernel(const NoisyParams p) {
             }
         }
     }
+}
+
+template <bool BACKWARD>
+__global__ __launch_bounds__(kBlock) void noisy_kernel(const NoisyParams p) {
+    noisy_chunk<BACKWARD>(p, p.draw_lo, p.draw_hi);
+}
+
+// sgw_noisy_weights_clocked, forward mode (the backward draws nothing: it launches noisy_kernel<true>): draw = clock->count, both words
+__global__ __launch_bounds__(kBlock) void noisy_clocked_kernel(const NoisyParams p, const sgw_learn_clock* clock) {
+    const uint64_t draw = learn_clock_count(clock);
+    noisy_chunk<false>(p, (uint32_t)draw, (uint32_t)(draw >> 32));
 }

@@ -7,6 +7,7 @@
 // when this was the row's last piece) are issued before the stores of the current one, so two pieces are in flight per wave.
 // Indices are wave-uniform: read from starts / envs, or recomputed by every wave from one Philox block (no index pre-pass).
 #pragma once
+#include "learn_clock.h"
 
 constexpr int kSamplePieces = 8;            // loads per lane and piece (dword variant); the 16-byte variant issues kSamplePieces / 2
 constexpr int kSampleMaxBlocks = 1536;      // grid cap: 6144 waves, 24 per CU on 256 CUs (all resident at once: the kernels reach 7 waves per
@@ -95,7 +96,8 @@ struct SamplePiece {
 
 // Frame j of sample k: the sample's (start, env) -- given or drawn --, the row's addresses, and (the wave of the sample's last stacked
 // frame, lane 0) the sample's scalars.
-__device__ __forceinline__ SampleRow sample_locate(const SampleParams& p, const int64_t k, const int j, const uint64_t counter, const int lane) {
+__device__ __forceinline__ SampleRow sample_locate(const SampleParams& p, const int64_t num_starts, const int64_t k, const int j, const uint64_t counter,
+                                                   const int lane) {
     const int F = p.F;
     int64_t t, e;
     if (p.starts) {
@@ -105,11 +107,11 @@ __device__ __forceinline__ SampleRow sample_locate(const SampleParams& p, const 
         // u32 numbers 2k and 2k + 1 of the stream: words (0, 1) or (2, 3) of block k >> 1
         const U4 b = philox4x32_10((uint32_t)(k >> 1), (uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)SGW_STREAM_SAMPLE, p.seed_lo, p.seed_hi);
         const bool odd = (k & 1) != 0;
-        t = __builtin_amdgcn_readfirstlane(__umulhi(odd ? b.z : b.x, (uint32_t)p.num_starts));
+        t = __builtin_amdgcn_readfirstlane(__umulhi(odd ? b.z : b.x, (uint32_t)num_starts));
         e = __builtin_amdgcn_readfirstlane(__umulhi(odd ? b.w : b.y, (uint32_t)p.num_envs));
     }
     SampleRow r;
-    const bool ok = t >= 0 && t < p.num_starts && e >= 0 && e < p.num_envs;      // a given index out of range: no address is formed from it
+    const bool ok = t >= 0 && t < num_starts && e >= 0 && e < p.num_envs;      // a given index out of range: no address is formed from it
     r.to_states = ok && j < F;
     r.to_next = ok && j >= 1;
     r.src = r.dst = 0;
@@ -136,8 +138,10 @@ __device__ __forceinline__ SampleRow sample_locate(const SampleParams& p, const 
     return r;
 }
 
+// the gather; num_starts bounds the drawn (and the given) starts: the argument block's (sample_rows_kernel) or the learner clock's, clamped
+// (sample_rows_clocked_kernel)
 template <int VEC, bool U8>
-__global__ __launch_bounds__(kBlock) void sample_rows_kernel(const SampleParams p) {
+__device__ __forceinline__ void sample_rows(const SampleParams& p, const int64_t num_starts) {
     const int lane = threadIdx.x & 63;
     const int F1 = p.F + 1;
     const uint32_t w0 = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // below the grid's wave count
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void sample_rows_kernel(const SampleParams 
     const uint64_t counter = p.starts ? 0 : (p.draw_count ? uniform_load(p.draw_count, 0) : p.draw);
     const int pieces = p.pieces;
     SamplePiece<VEC, U8> cur, nxt;
-    SampleRow row = sample_locate(p, k, j, counter, lane), nrow = row;
+    SampleRow row = sample_locate(p, num_starts, k, j, counter, lane), nrow = row;
     int c = 0;
     cur.load(p, row, c, lane);
     for (;;) {
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void sample_rows_kernel(const SampleParams 
                 ++k;
             }
             more = k < p.n;
-            if (more) nrow = sample_locate(p, k, j, counter, lane);
+            if (more) nrow = sample_locate(p, num_starts, k, j, counter, lane);
         }
         if (!more) nc = c;                  // (the last piece is loaded once more rather than branching around the loads)
         nxt.load(p, nrow, nc, lane);
@@ -173,6 +177,20 @@ __global__ __launch_bounds__(kBlock) void sample_rows_kernel(const SampleParams 
         row = nrow;
         c = nc;
     }
+}
+
+template <int VEC, bool U8>
+__global__ __launch_bounds__(kBlock) void sample_rows_kernel(const SampleParams p) {
+    sample_rows<VEC, U8>(p, p.num_starts);
+}
+
+// sgw_sample_clocked: the draws' bound is the learner clock's num_starts, read once and clamped HERE to [1, p.num_starts] -- the bound the host
+// checked against the ring's capacity -- so that whatever the clock holds, no row read lies outside the ring
+template <int VEC, bool U8>
+__global__ __launch_bounds__(kBlock) void sample_rows_clocked_kernel(const SampleParams p, const sgw_learn_clock* clock) {
+    const int64_t now = learn_clock_num_starts(clock);
+    const int64_t least = now > 1 ? now : 1;
+    sample_rows<VEC, U8>(p, least < p.num_starts ? least : p.num_starts);
 }
 
 // *count += 1, after the gather that read it (same stream): the next call -- or the next replay of a recorded graph -- draws anew

@@ -120,6 +120,8 @@ int workspace_short(const char* who, const void* ptr, const int64_t have, const 
 
 // one launch of kBlock-thread workgroups and the check behind it (a failure reads "hipGetLastError(): ...", as it always has)
 #define LAUNCH_TRY(kernel, blocks, s, p) do { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, p); HIP_TRY(hipGetLastError()); } while (0)
+// ... of a clocked twin: the same argument block with the learner clock's device address behind it
+#define LAUNCH_CLOCKED_TRY(kernel, blocks, s, p, clock) do { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, p, clock); HIP_TRY(hipGetLastError()); } while (0)
 
 constexpr int kEventPool = 4096;
 
@@ -1323,27 +1325,26 @@ int sgw_render(const sgw_render_desc* d, void* stream) {
 }
 
 // ---------------------------------------------------------------- replay batches (sample.h)
-int sgw_sample(const sgw_sample_desc* d, void* stream) {
-    if (!d) return fail(SGW_EINVAL, "sgw_sample: desc is NULL");
-    if (!d->states || !d->actions || !d->rewards || !d->dones) return fail(SGW_EINVAL, "sgw_sample: states, actions, rewards and dones must not be NULL");
+static int sample_launch(const sgw_sample_desc* d, const sgw_learn_clock* clock, const char* who, void* stream) {
+    if (!d->states || !d->actions || !d->rewards || !d->dones) return fail(SGW_EINVAL, "%s: states, actions, rewards and dones must not be NULL", who);
     if (!d->out_states || !d->out_next_states || !d->out_actions || !d->out_rewards || !d->out_dones || !d->out_valid)
-        return fail(SGW_EINVAL, "sgw_sample: every output except out_index must not be NULL");
-    if (d->n < 0) return fail(SGW_EINVAL, "sgw_sample: n = %lld", (long long)d->n);
-    if (d->n_frames < 1) return fail(SGW_EINVAL, "sgw_sample: n_frames = %d", d->n_frames);
-    if (d->row_elems < 1 || d->row_elems >= (1ll << 30)) return fail(SGW_EINVAL, "sgw_sample: row_elems = %lld outside [1, 2^30)", (long long)d->row_elems);   // (the kernels index a row's units in 32 bits, a piece past its end included)
-    if (d->num_envs < 1 || d->num_envs >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_sample: num_envs = %lld outside [1, 2^31)", (long long)d->num_envs);
-    if (d->num_starts < 1 || d->num_starts >= (1ll << 31)) return fail(SGW_EINVAL, "sgw_sample: num_starts = %lld outside [1, 2^31)", (long long)d->num_starts);
+        return fail(SGW_EINVAL, "%s: every output except out_index must not be NULL", who);
+    if (d->n < 0) return fail(SGW_EINVAL, "%s: n = %lld", who, (long long)d->n);
+    if (d->n_frames < 1) return fail(SGW_EINVAL, "%s: n_frames = %d", who, d->n_frames);
+    if (d->row_elems < 1 || d->row_elems >= (1ll << 30)) return fail(SGW_EINVAL, "%s: row_elems = %lld outside [1, 2^30)", who, (long long)d->row_elems);   // (the kernels index a row's units in 32 bits, a piece past its end included)
+    if (d->num_envs < 1 || d->num_envs >= (1ll << 31)) return fail(SGW_EINVAL, "%s: num_envs = %lld outside [1, 2^31)", who, (long long)d->num_envs);
+    if (d->num_starts < 1 || d->num_starts >= (1ll << 31)) return fail(SGW_EINVAL, "%s: num_starts = %lld outside [1, 2^31)", who, (long long)d->num_starts);
     if (d->num_starts + d->n_frames > d->capacity)
-        return fail(SGW_EINVAL, "sgw_sample: num_starts + n_frames = %lld exceeds the capacity %lld: the last row read must lie inside the ring", (long long)(d->num_starts + d->n_frames), (long long)d->capacity);
-    if (!d->starts != !d->envs) return fail(SGW_EINVAL, "sgw_sample: starts and envs are both given or both NULL");
-    if (d->src_type != SGW_SAMPLE_F32 && d->src_type != SGW_SAMPLE_U8) return fail(SGW_EINVAL, "sgw_sample: unknown src_type %d", d->src_type);
-    if (d->act_type != SGW_SAMPLE_ACT_I64 && d->act_type != SGW_SAMPLE_ACT_U8) return fail(SGW_EINVAL, "sgw_sample: unknown act_type %d", d->act_type);
+        return fail(SGW_EINVAL, "%s: num_starts + n_frames = %lld exceeds the capacity %lld: the last row read must lie inside the ring", who, (long long)(d->num_starts + d->n_frames), (long long)d->capacity);
+    if (!d->starts != !d->envs) return fail(SGW_EINVAL, "%s: starts and envs are both given or both NULL", who);
+    if (d->src_type != SGW_SAMPLE_F32 && d->src_type != SGW_SAMPLE_U8) return fail(SGW_EINVAL, "%s: unknown src_type %d", who, d->src_type);
+    if (d->act_type != SGW_SAMPLE_ACT_I64 && d->act_type != SGW_SAMPLE_ACT_U8) return fail(SGW_EINVAL, "%s: unknown act_type %d", who, d->act_type);
     const bool u8 = d->src_type == SGW_SAMPLE_U8;
     if (misaligned(3, {u8 ? nullptr : d->states, d->rewards, d->dones, d->out_states, d->out_next_states, d->out_rewards, d->out_dones, d->out_valid}))
-        return fail(SGW_EINVAL, "sgw_sample: misaligned float32 pointer");
+        return fail(SGW_EINVAL, "%s: misaligned float32 pointer", who);
     if (misaligned(7, {d->act_type == SGW_SAMPLE_ACT_I64 ? d->actions : nullptr, d->starts, d->envs, d->draw_count, d->out_actions, d->out_index}))
-        return fail(SGW_EINVAL, "sgw_sample: misaligned int64 pointer");
-    if (d->n > INT64_MAX / ((int64_t)d->n_frames + 1) / d->row_elems) return fail(SGW_EINVAL, "sgw_sample: n = %lld: the batch does not fit 64-bit offsets", (long long)d->n);
+        return fail(SGW_EINVAL, "%s: misaligned int64 pointer", who);
+    if (d->n > INT64_MAX / ((int64_t)d->n_frames + 1) / d->row_elems) return fail(SGW_EINVAL, "%s: n = %lld: the batch does not fit 64-bit offsets", who, (long long)d->n);
     if (d->n == 0) return SGW_OK;
     SampleParams p{};
     p.states = d->states; p.actions = d->actions; p.rewards = d->rewards; p.dones = d->dones;
@@ -1367,7 +1368,13 @@ int sgw_sample(const sgw_sample_desc* d, void* stream) {
     p.step_k = waves / (d->n_frames + 1);
     p.step_j = (int32_t)(waves % (d->n_frames + 1));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vec4 && u8) LAUNCH_TRY((sample_rows_kernel<4, true>), blocks, s, p);
+    if (clock) {
+        if (vec4 && u8) LAUNCH_CLOCKED_TRY((sample_rows_clocked_kernel<4, true>), blocks, s, p, clock);
+        else if (vec4) LAUNCH_CLOCKED_TRY((sample_rows_clocked_kernel<4, false>), blocks, s, p, clock);
+        else if (u8) LAUNCH_CLOCKED_TRY((sample_rows_clocked_kernel<1, true>), blocks, s, p, clock);
+        else LAUNCH_CLOCKED_TRY((sample_rows_clocked_kernel<1, false>), blocks, s, p, clock);
+    }
+    else if (vec4 && u8) LAUNCH_TRY((sample_rows_kernel<4, true>), blocks, s, p);
     else if (vec4) LAUNCH_TRY((sample_rows_kernel<4, false>), blocks, s, p);
     else if (u8) LAUNCH_TRY((sample_rows_kernel<1, true>), blocks, s, p);
     else LAUNCH_TRY((sample_rows_kernel<1, false>), blocks, s, p);
@@ -1375,6 +1382,34 @@ int sgw_sample(const sgw_sample_desc* d, void* stream) {
         hipLaunchKernelGGL(sample_count_kernel, dim3(1), dim3(64), 0, s, d->draw_count);
         HIP_TRY(hipGetLastError());
     }
+    return SGW_OK;
+}
+
+int sgw_sample(const sgw_sample_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_sample: desc is NULL");
+    return sample_launch(d, nullptr, "sgw_sample", stream);
+}
+
+// ---------------------------------------------------------------- the learner clock (learn_clock.h)
+// SGW_OK, or the refusal of a clock that is missing or not 8-byte aligned
+static int clock_refused(const char* who, const sgw_learn_clock* clock) {
+    if (!clock) return fail(SGW_EINVAL, "%s: clock is NULL", who);
+    if (misaligned(7, {clock})) return fail(SGW_EINVAL, "%s: misaligned clock (a device address that is a multiple of 8)", who);
+    return SGW_OK;
+}
+
+int sgw_sample_clocked(const sgw_sample_desc* d, const sgw_learn_clock* clock, void* stream) {
+    const char* who = "sgw_sample_clocked";
+    if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
+    if (int rc = clock_refused(who, clock)) return rc;
+    if (d->starts || d->envs) return fail(SGW_EINVAL, "%s: starts and envs must be NULL (the clock bounds drawn indices; given ones take sgw_sample)", who);
+    return sample_launch(d, clock, who, stream);
+}
+
+int sgw_learn_clock_advance(sgw_learn_clock* clock, void* stream) {
+    if (int rc = clock_refused("sgw_learn_clock_advance", clock)) return rc;
+    hipLaunchKernelGGL(learn_clock_advance_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), clock);
+    HIP_TRY(hipGetLastError());
     return SGW_OK;
 }
 
@@ -1591,7 +1626,7 @@ int64_t sgw_iqn_forward_workspace_bytes(int64_t n, int32_t layer_size) {
     return n * layer_size * (int64_t)sizeof(float);
 }
 
-static int iqn_forward_launch(const sgw_iqn_forward_desc* d, const TurnState* ts, const char* who, void* stream) {
+static int iqn_forward_launch(const sgw_iqn_forward_desc* d, const TurnState* ts, const char* who, void* stream, const sgw_learn_clock* clock = nullptr) {
     if (int rc = iqn_network_check(d, who, 63)) return rc;
     if (!d->out_qvalues && !d->out_quantiles) return fail(SGW_EINVAL, "%s: one of out_qvalues and out_quantiles must be given", who);
     if (!d->taus) {                           // the draw's key
@@ -1624,7 +1659,9 @@ static int iqn_forward_launch(const sgw_iqn_forward_desc* d, const TurnState* ts
     if (p.u8) hipLaunchKernelGGL(iqn_head_kernel<true>, head_grid, dim3(kFwdThreads), 0, s, p);
     else hipLaunchKernelGGL(iqn_head_kernel<false>, head_grid, dim3(kFwdThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(iqn_quantile_kernel, dim3((unsigned)std::min<int64_t>(p.q_tiles, kFwdMaxBlocks)), dim3(kFwdThreads), 0, s, p);
+    const dim3 q_grid((unsigned)std::min<int64_t>(p.q_tiles, kFwdMaxBlocks));
+    if (clock) hipLaunchKernelGGL(iqn_quantile_clocked_kernel, q_grid, dim3(kFwdThreads), 0, s, p, clock);
+    else hipLaunchKernelGGL(iqn_quantile_kernel, q_grid, dim3(kFwdThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
     return SGW_OK;
 }
@@ -1632,6 +1669,15 @@ static int iqn_forward_launch(const sgw_iqn_forward_desc* d, const TurnState* ts
 int sgw_iqn_forward(const sgw_iqn_forward_desc* d, void* stream) {
     if (!d) return fail(SGW_EINVAL, "sgw_iqn_forward: desc is NULL");
     return iqn_forward_launch(d, nullptr, "sgw_iqn_forward", stream);
+}
+
+int sgw_iqn_forward_clocked(const sgw_iqn_forward_desc* d, const sgw_learn_clock* clock, void* stream) {
+    const char* who = "sgw_iqn_forward_clocked";
+    if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
+    if (int rc = clock_refused(who, clock)) return rc;
+    if (d->turn) return fail(SGW_EINVAL, "%s: turn = %u must be 0 (the drawn taus' turn is the clock's count)", who, d->turn);
+    if (d->taus) return fail(SGW_EINVAL, "%s: taus must be NULL (given taus need no clock: sgw_iqn_forward)", who);
+    return iqn_forward_launch(d, nullptr, who, stream, clock);
 }
 
 int sgw_turn_iqn_forward(sgw_engine* e, int32_t agent, const sgw_iqn_forward_desc* desc, void* stream) {
@@ -1703,9 +1749,7 @@ int sgw_iqn_backward(const sgw_iqn_backward_desc* d, void* stream) {
 }
 
 // ---------------------------------------------------------------- the noisy layers' weights (noisy.h)
-int sgw_noisy_weights(const sgw_noisy_weights_desc* d, void* stream) {
-    const char* who = "sgw_noisy_weights";
-    if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
+static int noisy_launch(const sgw_noisy_weights_desc* d, const sgw_learn_clock* clock, const char* who, void* stream) {
     if (d->mode != SGW_NOISY_FORWARD && d->mode != SGW_NOISY_BACKWARD) return fail(SGW_EINVAL, "%s: unknown mode %d", who, d->mode);
     if (d->num_jobs < 0 || d->num_jobs > SGW_NOISY_MAX_JOBS) return fail(SGW_EINVAL, "%s: num_jobs = %d outside [0, %d]", who, d->num_jobs, SGW_NOISY_MAX_JOBS);
     if (d->reserved0 || d->reserved1) return fail(SGW_EINVAL, "%s: reserved fields must be 0", who);
@@ -1743,9 +1787,23 @@ int sgw_noisy_weights(const sgw_noisy_weights_desc* d, void* stream) {
     p.seed_lo = (uint32_t)d->seed; p.seed_hi = (uint32_t)(d->seed >> 32);
     p.draw_lo = (uint32_t)d->draw; p.draw_hi = (uint32_t)(d->draw >> 32);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (backward) LAUNCH_TRY(noisy_kernel<true>, (unsigned)chunks, s, p);
+    if (backward) LAUNCH_TRY(noisy_kernel<true>, (unsigned)chunks, s, p);               // (draws nothing: the clock is not read)
+    else if (clock) LAUNCH_CLOCKED_TRY(noisy_clocked_kernel, (unsigned)chunks, s, p, clock);
     else LAUNCH_TRY(noisy_kernel<false>, (unsigned)chunks, s, p);
     return SGW_OK;
+}
+
+int sgw_noisy_weights(const sgw_noisy_weights_desc* d, void* stream) {
+    if (!d) return fail(SGW_EINVAL, "sgw_noisy_weights: desc is NULL");
+    return noisy_launch(d, nullptr, "sgw_noisy_weights", stream);
+}
+
+int sgw_noisy_weights_clocked(const sgw_noisy_weights_desc* d, const sgw_learn_clock* clock, void* stream) {
+    const char* who = "sgw_noisy_weights_clocked";
+    if (!d) return fail(SGW_EINVAL, "%s: desc is NULL", who);
+    if (int rc = clock_refused(who, clock)) return rc;
+    if (d->draw) return fail(SGW_EINVAL, "%s: draw = %llu must be 0 (the draw is the clock's count)", who, (unsigned long long)d->draw);
+    return noisy_launch(d, clock, who, stream);
 }
 
 // ---------------------------------------------------------------- Adam, clipping and the soft update (adam_step.h)

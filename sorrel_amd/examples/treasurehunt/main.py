@@ -2,7 +2,9 @@
 
 The default agents act at random (``RandomModel``: the whole epoch is one engine call).  ``--model iqn`` gives every agent a
 ``sorrel_amd.models.PyTorchIQN`` built from ``config.model.*`` with the reference's keys (``sorrel/examples/treasurehunt/env.py:80-99``): the
-agents act through the network, fill its replay ring and learn after every epoch."""
+agents act through the network, fill its replay ring and learn after every epoch.  ``--capture-train`` records the learner's step as a graph
+at its first update (``config.model.capture_train_step``); ``config.model.updates_per_call`` makes several updates per epoch (default 1, the
+reference's)."""
 import sys
 
 from sorrel_amd.examples.treasurehunt.entities import EmptyEntity
@@ -25,7 +27,8 @@ def make_config(height=21, width=21, num_agents=2, radius=2, spawn_prob=0.005, e
 
 def iqn_model_factory(config, num_envs, device=None, seed=0):
     """A ``model_factory`` for ``TreasurehuntEnv``: every agent gets its own ``PyTorchIQN`` from ``config["model"]`` (``IQN_DEFAULTS`` for
-    the keys it leaves out), with a replay ring over ``num_envs`` envs; agent ``k``'s seed is ``seed + k``."""
+    the keys it leaves out), with a replay ring over ``num_envs`` envs; agent ``k``'s seed is ``seed + k``.  ``updates_per_call`` (default 1) and
+    ``capture_train_step`` (default False: the model records its step at its first gated ``train_step``) are this package's keys."""
     from sorrel_amd.models import PyTorchIQN
 
     model = config["model"]
@@ -34,6 +37,8 @@ def iqn_model_factory(config, num_envs, device=None, seed=0):
 
     def factory(input_size, action_space):
         made.append(PyTorchIQN(input_size, action_space, device=device, seed=seed + len(made), num_envs=num_envs, **args))
+        made[-1].updates_per_call = int(model.get("updates_per_call", 1))
+        made[-1].capture_lazily = bool(model.get("capture_train_step", False))
         return made[-1]
 
     return factory
@@ -56,6 +61,7 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     kind = argv[argv.index("--model") + 1] if "--model" in argv else "random"
     config = make_config()
+    config["model"]["capture_train_step"] = "--capture-train" in argv
     env = make_env(config, 4096 if kind == "random" else 256, kind)
     for epoch, m in enumerate(env.run_experiment()):
         print(f"epoch {epoch}: mean total_reward over {int(m['envs'])} envs = {m['mean_total_reward']:.3f}" +

@@ -257,7 +257,8 @@ class IQN(nn.Module):
         return B, flat, N, res
 
     def _launch_forward(self, flat, ws, res: IQNOutput, taus=None, key=None, cos: bool = False, engine=None, agent: Optional[int] = None):
-        """One ``sgw_iqn_forward`` call (or ``sgw_turn_iqn_forward``) over checked arguments: ``ws`` are the ten effective weights."""
+        """One ``sgw_iqn_forward`` call (or ``sgw_turn_iqn_forward``) over checked arguments: ``ws`` are the ten effective weights.
+        ``key["clock"]`` (the device address of an ``sgw_learn_clock``) makes it ``sgw_iqn_forward_clocked``: the drawn taus' turn is the clock's."""
         B, N, A = res.quantiles.shape
         L, dev = int(self.layer_size), flat.device
         for w in ws:
@@ -271,7 +272,7 @@ class IQN(nn.Module):
         if res.cos is not None and cos:
             d.out_cos = res.cos.data_ptr()
         d.workspace, d.workspace_bytes = res._workspace.data_ptr(), res._workspace.numel() * 8
-        keep = None
+        keep = clock = None
         if taus is not None:
             d.taus = taus.data_ptr()
         elif engine is None:
@@ -281,7 +282,7 @@ class IQN(nn.Module):
             d.seed = int(key.get("seed", self.key_seed)) & 0xFFFFFFFFFFFFFFFF
             d.epoch, d.turn = int(key.get("epoch", 0)), int(key.get("turn", self._calls)) & 0xFFFFFFFF
             d.num_envs, d.agent0, d.first_env = int(key.get("num_envs", max(B, 1))), int(key.get("agent0", 0)), int(key.get("first_env", 0))
-            keep = key.get("idx")
+            keep, clock = key.get("idx"), key.get("clock")
             if keep is not None:
                 if keep.dtype != torch.int64 or tuple(keep.shape) != (B,) or not keep.is_contiguous() or keep.device != dev:
                     raise ValueError(f"key['idx'] must be contiguous int64 [{B}] on {dev}")
@@ -291,7 +292,7 @@ class IQN(nn.Module):
                 raise ValueError(f"the turn protocol's rows are the engine's {engine.num_envs} envs; got {B}")
             N_.launch("sgw_turn_iqn_forward", d, dev, engine._h, int(agent or 0))
         else:
-            N_.launch("sgw_iqn_forward", d, dev)
+            N_.launch("sgw_iqn_forward", d, dev, clock=clock)
         return res
 
     # ------------------------------------------------------------------------------------------------ the device path with autograd

@@ -113,6 +113,15 @@ class FusedAdam(torch.optim.Optimizer):
             tb.pending = 0
             tb.step = step
 
+    def count_on_device(self, on: bool = True) -> None:
+        """Switch ``device_step``: the count so far is flushed into ``state[p]['step']`` and the tables are dropped, so the next ``step()`` rebuilds
+        them (an upload: not inside a capture) and goes on from the same count.  (The bias corrections then come from running products of the
+        betas, not ``pow``: the bits differ from the default's in the last place.)"""
+        if bool(on) != self.device_step:
+            self._flush()
+            self.device_step = bool(on)
+            self._key, self._tables = None, []
+
     def state_dict(self):
         self._flush()
         return super().state_dict()
@@ -132,6 +141,14 @@ class FusedAdam(torch.optim.Optimizer):
                 raise ValueError("FusedAdam: weight decay, amsgrad and maximize are out of scope")
         return float(betas[0]), float(betas[1]), float(eps)
 
+    def _table_key(self, active):
+        targets = self._targets
+        return tuple((p.data_ptr(), p.grad.data_ptr(), targets[id(p)].data_ptr() if targets else 0, lr) for p, lr in active)
+
+    def table_key(self):
+        """What the uploaded table was built from, computed from the tensors as they lie now: ``step()`` rebuilds when it differs."""
+        return self._table_key([(p, float(g["lr"])) for g in self.param_groups for p in g["params"] if p.grad is not None])
+
     @torch.no_grad()
     def step(self, closure=None):
         if closure is not None:
@@ -144,8 +161,7 @@ class FusedAdam(torch.optim.Optimizer):
             return self._step_torch([p for p, _ in active])
         if devices != {"cuda"}:
             raise ValueError(f"FusedAdam: the parameters lie on {sorted(devices)}; one call takes CPU tensors or device tensors")
-        targets = self._targets
-        key = tuple((p.data_ptr(), p.grad.data_ptr(), targets[id(p)].data_ptr() if targets else 0, lr) for p, lr in active)
+        key = self._table_key(active)
         if key != self._key:
             self._build(active)
             self._key = key

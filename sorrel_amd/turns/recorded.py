@@ -179,20 +179,10 @@ class CapturedTurn:
                 raise RuntimeError("an agent's add_memory did not run once per turn")
         before = [(mem.idx, mem.size) for mem in self.buffers]
         g = torch.cuda.CUDAGraph()
-        # No garbage collection inside the capture: an unreachable engine or graph of an EARLIER environment that the collector happens to
-        # free now would call hipFree / hipGraphDestroy while a stream is capturing, which HIP forbids -- the capture fails, and torch aborts
-        # the process while it unwinds (seen under rocprofv3, where the timing differs; torch.cuda.graph no longer collects on entry itself)
-        # The window: process-wide and NOT thread-safe (another thread that re-enables the collector, or drops the last reference to an engine /
-        # graph between here and the end of the capture, still frees inside it) -- a capture is a single-threaded moment of the caller's program.
-        # Reference-counted frees of THIS thread are kept out explicitly: engines whose close() is pending are closed now, before the capture.
-        import gc
-        from sorrel_amd.engine import GridEngine
-        gc.collect()
-        GridEngine.drain_pending_closes()
-        gc_was_on = gc.isenabled()
-        gc.disable()
+        # (no garbage collection and no pending engine close inside the capture: sorrel_amd.capture.recording says why)
+        from sorrel_amd.capture import recording
         try:
-            with torch.cuda.graph(g):
+            with recording(g):
                 env._turn_protocol_body(eng)              # recorded, not run: the host-side effects are undone below
         except BaseException:
             import os, sys, traceback
@@ -201,15 +191,12 @@ class CapturedTurn:
                 print(env.capture_error_trace, file=sys.stderr, flush=True)
             raise
         finally:
-            if gc_was_on:
-                gc.enable()
             # ... also when the capture fails half-way (a later agent's forward pass synchronises): the agents before it have already
             # counted an add_memory for rows that were never written -- the eager loop must not find them counted as valid
             for mem, (idx, size) in zip(self.buffers, before):
                 mem.idx, mem.size = idx, size
                 mem._deferred_adds = 0
         self.graph = g
-        GridEngine.drain_pending_closes()
         self._expect, self._at = [mem.idx for mem in self.buffers], (env.epoch, env.turn)
 
     def abort(self) -> None:

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""A whole IQN learner step three ways.  Prints the text of profiles/iqn_learner.txt.
+"""A whole IQN learner step four ways.  Prints the text of profiles/iqn_learner.txt (profiles/iqn_learner_recorded.txt since the recorded column).
 
 usage: python tools/bench_iqn_learner.py [--reps 20] [--out FILE]
-       python tools/bench_iqn_learner.py --only device|hand|torch --batch 64 --steps 10      (one path alone, for a kernel trace)
+       python tools/bench_iqn_learner.py --only device|recorded|hand|torch --batch 64 --steps 10      (one path alone, for a kernel trace)
        python tools/bench_iqn_learner.py --sum-calls DIR                                       (total of the Calls column of a trace's *kernel_stats.csv)
 
 The reference's shape (in_features 875, layer_size 250, 12 quantiles, 4 actions), batches of 64 (the reference's), 1 024 and 4 096 states
 sampled from a replay ring of twice the batch; the reference's hyper-parameters.  The paths:
 
 * ``device``: ``PyTorchIQN.train_step()`` on the device (sgw_sample, sgw_noisy_weights, 3 x sgw_iqn_forward, sgw_iqn_loss, sgw_iqn_backward,
-  sgw_noisy_weights backwards, sgw_adam_step, one copy of the loss);
+  sgw_noisy_weights backwards, sgw_adam_step, one copy of the loss).  It is the BASELINE of the recorded path (the same code before and
+  after that path existed) and is timed in two series per round, so that its own spread is known;
+* ``recorded``: the same step after ``capture_train_step()``: one graph replay (the clocked twins of the three calls that take the step's count
+  or the ring's filled rows, ``sgw_learn_clock_advance`` last);
 * ``hand``: the hand-written step of ``sorrel_amd/losses.py``'s docstring from public calls (``Buffer.sample``, ``IQN.quantiles`` x 2,
   ``IQN.forward_fused``, ``iqn_loss``, ``backward()``, ``FusedAdam.step()``): what the package offered before the learner class, and the
   BASELINE: it is timed twice per round, and the difference of its two medians is the spread a difference between paths has to exceed;
@@ -17,7 +20,9 @@ sampled from a replay ring of twice the batch; the reference's hyper-parameters.
   soft-update loop.
 
 One process; device events around each step; after a warm-up the paths alternate step by step and the order is reversed every other round.
-Each path owns its networks and optimiser (same start).  Nothing is asserted about speed; the numbers are reported as they come.  The
+Each path owns its networks and optimiser (same start).  Behind the event times: wall time per step over ``--wall`` back-to-back steps of
+the eager and the recorded ``train_step`` (one synchronisation at the end), which is where host time shows.  Nothing is asserted about
+speed; the numbers are reported as they come.  The
 launch counts per step come from a kernel trace of each path alone (``--only``), taken as the difference of two runs of different length."""
 import argparse
 import csv
@@ -99,14 +104,18 @@ def make_paths(B, dev):
             target_param.data.copy_(HYPER["TAU"] * local_param.data + (1.0 - HYPER["TAU"]) * target_param.data)
         return loss
 
-    return dict(device=device_model.train_step, hand=by_hand, torch=by_torch)
+    recorded_model = learner()
+    recorded_model.capture_train_step(warmup=2)
+
+    return dict(device=device_model.train_step, recorded=recorded_model.train_step, hand=by_hand, torch=by_torch)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("device", "hand", "torch"), default=None)
+    ap.add_argument("--only", choices=("device", "recorded", "hand", "torch"), default=None)
+    ap.add_argument("--wall", type=int, default=200)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--sum-calls", default=None)
@@ -130,10 +139,13 @@ def main():
     emit = Emitter(args.out, as_it_grows=True)
     emit(f"# tools/bench_iqn_learner.py --reps {args.reps}: {torch.cuda.get_device_name(0)}; in_features {OBS}, layer_size {L}, {NQ} quantiles, {A} actions; "
          f"microseconds per learner step (sampling the batch included), device events around each step, paths alternating step by step "
-         f"(hand, device, torch, hand; the order reversed every other round)")
+         f"(hand, device, recorded, torch, device, hand; the order reversed every other round); wall time per step over {args.wall} back-to-back steps")
+    import time
+
     for B in BATCHES:
         paths = make_paths(B, dev)
-        order = [("hand", paths["hand"]), ("device", paths["device"]), ("torch", paths["torch"]), ("hand2", paths["hand"])]
+        order = [("hand", paths["hand"]), ("device", paths["device"]), ("recorded", paths["recorded"]), ("torch", paths["torch"]),
+                 ("device2", paths["device"]), ("hand2", paths["hand"])]
         for _ in range(3):
             for _, f in order:
                 f()
@@ -144,15 +156,30 @@ def main():
                 times[name].append(one(f))
         (m1, lo1, hi1), (m2, _, _) = stats(times["hand"]), stats(times["hand2"])
         (md, lod, hid), (mt, lot, hit) = stats(times["device"]), stats(times["torch"])
+        (md2, _, _), (mr, lor, hir) = stats(times["device2"]), stats(times["recorded"])
         spread, base = abs(m1 - m2), 0.5 * (m1 + m2)
+        dspread, dbase = abs(md - md2), 0.5 * (md + md2)
 
         def verdict(m):
             return ("faster than the hand-written step by more than the spread" if m < base - spread else
                     "SLOWER than the hand-written step by more than the spread" if m > base + spread else "within the spread of the hand-written step")
 
         emit(f"B={B:<5} hand-written step   {m1:9.1f} / {m2:9.1f} us (p10 {lo1:.1f}, p90 {hi1:.1f}; spread of the medians {spread:.1f})")
-        emit(f"{'':8}train_step (device) {md:9.1f} us (p10 {lod:.1f}, p90 {hid:.1f})  x {base / md:6.2f}  {verdict(md)}")
+        emit(f"{'':8}train_step (device) {md:9.1f} / {md2:9.1f} us (p10 {lod:.1f}, p90 {hid:.1f}; spread of the medians {dspread:.1f})  x {base / md:6.2f}  {verdict(md)}")
+        emit(f"{'':8}train_step recorded {mr:9.1f} us (p10 {lor:.1f}, p90 {hir:.1f})  x {dbase / mr:6.2f} of the eager train_step: " +
+             ("faster by more than its spread" if mr < dbase - dspread else "SLOWER by more than its spread" if mr > dbase + dspread else "within its spread"))
         emit(f"{'':8}all-torch step      {mt:9.1f} us (p10 {lot:.1f}, p90 {hit:.1f})  x {base / mt:6.2f}  {verdict(mt)}")
+        wall = {}
+        for name in ("device", "recorded", "device2"):
+            f = paths[name.rstrip("2")]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.wall):
+                f()
+            torch.cuda.synchronize()
+            wall[name] = (time.perf_counter() - t0) * 1e6 / args.wall
+        emit(f"{'':8}wall per step, {args.wall} back to back: eager {wall['device']:.1f} / {wall['device2']:.1f} us, recorded {wall['recorded']:.1f} us "
+             f"(x {0.5 * (wall['device'] + wall['device2']) / wall['recorded']:.2f})")
     emit.close()
 
 
